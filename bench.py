@@ -2,6 +2,7 @@
 """Benchmark of the RankAAE training-step hot path on MI355X (BASELINE.json metric).
 
     python bench.py --gpus N --steps K --warmup W [--ae-form compact|FC] [--batch 256]
+                    [--dump-outputs DIR] [--full]
 
 With ``--gpus N`` and no launcher (WORLD_SIZE unset) it starts its N rank processes itself.
 One "step" = the reference's five-phase update (adversarial, rank, reconstruction,
@@ -10,10 +11,18 @@ updates; ``sc/clustering/trainer.py:103-204``) on one batch of 256 synthetic 256
 spectra drawn from a device-resident 7000-row dataset (BASELINE.json ``configs[1]``).
 Rank 0 prints ONE JSON line.  ``value`` = batch-256 steps per second summed over all
 ranks (weak scaling: every GPU steps its own 256-row shard of a 256*N global batch and
-the five gradient arenas are averaged over RCCL).  The line also carries:
-  roofline      the dominant kernel of this workload: algorithmic bytes / HIP-event time
-  cpu_baseline  the CPU oracle (PyTorch fp32 autograd restatement of the reference) timed on
-                this box's host cores: 1 thread + anomaly detection on, as the reference ships
+the five gradient arenas are averaged over RCCL); ``ms_per_step`` = milliseconds of one
+timed step.  A plain run sets up, warms up, times the K steps, writes the last step's
+outputs if ``--dump-outputs DIR`` is given, and prints that line.  With ``--full`` (one
+GPU) the line also carries:
+  roofline           the dominant kernel of this workload: algorithmic bytes / HIP-event time
+  epoch_inclusive    Trainer.train with its per-epoch validation, metrics and scheduler
+  configs2           BASELINE configs[2]: 100 k rows, batch 4096
+  concurrent_trials  T independent trials on the one GPU (engines and TrialBatch)
+  cpu_baseline       the CPU oracle (PyTorch fp32 autograd restatement of the reference) timed on
+                     the host's cores: 1 thread + anomaly detection on, as the reference ships
+(``--no-roofline``, ``--no-epoch``, ``--no-configs2``, ``--no-trials`` and ``--cpu-budget 0``
+leave single ones out.)
 """
 import argparse
 import gc
@@ -234,6 +243,21 @@ def quiet_gc():
     gc.freeze()
 
 
+def dump_outputs(out_dir, eng, nets):
+    """``--dump-outputs DIR``: what the timed path hands its caller after the last timed step, one ``DIR/<name>.npy``
+    each -- the step's losses (``loss.<key>.npy``, float64 of the device's fp32 values) and every floating-point
+    tensor of the three networks' state (``<network>.<state_dict key>.npy``, float32: the weights AdamW has just
+    updated and the BatchNorm running statistics).  Under 0.3 MB in all at the bench shapes.  The inputs are seeded
+    (data, initial weights, epoch permutations, the device RNG), so the same arguments give the same inputs."""
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in eng.losses().items():
+        np.save(os.path.join(out_dir, f"loss.{k}.npy"), np.array([v], dtype=np.float64))
+    for name, net in nets:
+        for k, v in net.state_dict().items():
+            if v.is_floating_point():
+                np.save(os.path.join(out_dir, f"{name}.{k}.npy"), v.detach().to(torch.float32).cpu().numpy())
+
+
 def configs2_line(args, cfg0, dev):
     """BASELINE configs[2] beside the headline: 100 k synthetic spectra, batch 4096 -- the regime where the conv
     kernels stop being launch-bound.  Same engine, same step; returns steps/s and the top kernels' roofline."""
@@ -402,6 +426,12 @@ def main():
     ap.add_argument("--trials", type=str, default="1,4,8", help="engine counts of the concurrent-trials sub-run")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="override an engine tuning key (side_streams, overlap_unused_forwards, fused_blocks)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra measurements (roofline, epoch-inclusive, configs2, concurrent trials, "
+                         "CPU baseline; one GPU only); a plain run times the headline steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's losses and the updated network state "
+                         "as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -488,6 +518,8 @@ def main():
         dt = float(t)
     losses = eng.losses()
     finite = all(np.isfinite(v) for v in losses.values())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, (("encoder", enc), ("decoder", dec), ("discriminator", dis)))
 
     if rank == 0:
         value = world * args.steps / dt
@@ -510,18 +542,19 @@ def main():
                                                                else f"torch.distributed {dist.get_backend()} between graph segments"))},
             "losses_finite": finite, "last_losses": {k: round(v, 6) for k, v in losses.items()},
         }
-        # the extras run on ONE GPU only: with several ranks the probe's extra training steps would enter
-        # collectives the other ranks never join, and the contract asks for the CPU baseline at N = 1
-        if not args.no_roofline and world == 1:
+        # the extras run with --full and on ONE GPU only: with several ranks the probe's extra training steps would
+        # enter collectives the other ranks never join, and the contract asks for the CPU baseline at N = 1
+        extras = args.full and world == 1
+        if not args.no_roofline and extras:
             line["roofline"] = eng.roofline_probe(b, HBM_PEAK_GBS, detail=args.roofline_detail)
             annotate(line["roofline"], cfg["ae_form"], b)
             if b < 1024:
                 line["roofline"]["note"] = ("this batch is launch/latency bound (SURVEY 8d): every kernel moves <= 2.5 MB; "
                                             "the HBM-bound regime is the configs2 sub-run below")
-        if not args.no_epoch and world == 1:
+        if not args.no_epoch and extras:
             line["epoch_inclusive"] = epoch_inclusive(cfg, spec, aux)
-        big = not args.no_configs2 and world == 1 and (b, args.rows) == (256, 7000)
-        if (big or not args.no_trials) and world == 1:
+        big = not args.no_configs2 and extras and (b, args.rows) == (256, 7000)
+        if (big or not args.no_trials) and extras:
             del eng
             gc.unfreeze()
             gc.collect()
@@ -531,9 +564,9 @@ def main():
         # of 255-275)
         if big:
             line["configs2"] = configs2_line(args, cfg, dev)
-        if not args.no_trials and world == 1 and b <= 1024:
+        if not args.no_trials and extras and b <= 1024:
             line["concurrent_trials"] = trials_line(args, cfg, dev, spec, aux, tuple(int(x) for x in args.trials.split(",")))
-        if args.cpu_budget > 0 and world == 1:
+        if args.cpu_budget > 0 and extras:
             line["cpu_baseline"] = cpu_baseline(cfg, spec, aux, args.cpu_budget)
             ratio = cpu_calibration(cfg["ae_form"])
             if ratio:
