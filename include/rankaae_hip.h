@@ -476,8 +476,10 @@ int raae_step_begin(const raae_step_begin_t* p, void* stream);
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step) exist in a second form whose grid
- * plane z works on trial z's argument block.  raae_record_begin/end log the launches one trial makes on the calling
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step) and of the conv networks' fused
+ * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
+ * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
+ * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
  * thread (they still run); raae_multi_build takes the logs of T structurally identical trials and uploads, launch by
  * launch, the T argument blocks as one table (RAAE_EINVAL when the logs differ in kernel instance, geometry or LDS);
  * raae_multi_launch replays the program with gridDim.z = T on `stream` (capturable).  A trial's arithmetic is the body
@@ -489,6 +491,11 @@ int raae_multi_build(void* const* handles, int T, void** program);
 int raae_multi_launch(void* program, void* stream);
 int raae_multi_count(void* program);
 int raae_multi_free(void* program);
+/* Why the calling thread's last raae_record_end or raae_multi_build returned RAAE_EINVAL (ABI 17): the name of the first
+ * kernel launched during the recording without a batched form (e.g. "conv_fwd_tiled_kernel<false>"), or which launch of
+ * which trial differed.  Copies it NUL-terminated into buf[0..n) and returns its full length (0: nothing refused since
+ * the last raae_record_begin). */
+int raae_record_refusal(char* buf, int n);
 
 /* ---- launch-geometry hint (round 3; thread-local) ----------------------------------------------------------------------
  * The conv-network entry points size a workgroup's group of samples from the batch they are called with: at 256 rows a
@@ -525,7 +532,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 16
+#define RAAE_ABI_VERSION 17
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -6,11 +6,12 @@ engine.  The ipyparallel engine farm (``train_sc.py:19-45``) becomes one worker 
 trial ``k`` runs on worker ``k mod n`` and worker ``w`` uses GPU ``w mod ngpus`` (``RANKAAE_TRIAL_WORKERS``
 overrides ``n``).  Several trials share a GPU (config key ``trials_per_gpu``, default 4 when ``trials > 1``): a 256-row
 step is one serial chain of ~10 us kernels that leaves most of the chip idle, and the chains of independent trials
-overlap on it.  ``trial_mode: auto`` (default) picks ``batched`` for the dense networks -- the trials of a group train in
-LOCKSTEP and every training step of the group is ONE launch sequence whose kernels run with ``gridDim.z = trials``
-(``rankaae_amd/trial_batch.py``; 6.2x the single-trial rate at 8 trials, 10x at 16) -- and ``threads`` for the conv
-networks.  ``trial_mode: threads``: the trials of a worker run in threads of ONE process -- one engine,
-HIP stream and captured graph per trial, all of them feeding the same device; every trial draws from its own host
+overlap on it.  ``trial_mode: auto`` (default) picks ``batched`` (``choose_trial_mode``) -- the trials of a group train
+in LOCKSTEP and every training step of the group is ONE launch sequence whose kernels run with ``gridDim.z = trials``
+(``rankaae_amd/trial_batch.py``; dense networks 6.2x the single-trial rate at 8 trials, 10x at 16) -- for both
+networks at every batch size with ``rng_mode: philox`` and fp32, and ``threads`` otherwise.  ``trial_mode: threads``:
+the trials of a worker run in threads of ONE process -- one engine, HIP stream and captured graph per trial, all of
+them feeding the same device; every trial draws from its own host
 generator (seeded ``trial_seed + k``; ``trial_seed`` defaults to a draw from the global generator), so a trial's result
 does not depend on what runs beside it (tests/test_trainer_gpu.py).  ``trial_mode: processes``: one worker process per
 concurrent trial, as in round 2.  When launched under
@@ -28,7 +29,6 @@ import time
 import numpy as np
 import torch
 
-from rankaae_amd import _lib
 from rankaae_amd.logger import create_logger
 from rankaae_amd.parameter import Parameters
 from rankaae_amd.trainer import Trainer
@@ -133,15 +133,14 @@ def _trial_worker(worker, jobs, work_dir, config_dict, verbose, data_file, timeo
 
 def run_trials_batched(jobs, per_batch, work_dir, train_config, verbose, data_file, timeout, trial_seed, auto=False):
     """The trials ``jobs`` of this process, ``per_batch`` at a time, each group trained in LOCKSTEP: every training step
-    of the group is one launch sequence with ``gridDim.z = trials`` (``rankaae_amd.trainer.train_trials_batched``; dense
+    of the group is one launch sequence with ``gridDim.z = trials`` (``rankaae_amd.trainer.train_trials_batched``; both
     networks).  Seeds, files and log lines per trial as in the thread mode: ``[(k, metrics, time_used)]``."""
     from rankaae_amd.trainer import train_trials_batched
+    from rankaae_amd.trial_batch import BatchingRefused
     plain_config = train_config
     if train_config.get("ae_form", None) != "FC" and train_config.get("tile_rows_mult", None) is None:
-        # conv networks: every trial's launches sized as its share of a 4x larger batch (raae_tile_hint; +33 % at 8
-        # trials, +48 % at 16).  Keyed on the trial MODE, not on the group size: a trial's result is the same whatever
-        # runs beside it
-        train_config = Parameters({**train_config.to_dict(), "tile_rows_mult": 4})
+        train_config = Parameters({**train_config.to_dict(),
+                                   "tile_rows_mult": batched_tile_rows_mult(train_config.get("batch_size", 0))})
     ngpus = torch.cuda.device_count()
     local_id = int(os.environ.get("LOCAL_RANK", os.environ.get("SLURM_LOCALID", 0)))
     igpu = local_id % ngpus if ngpus > 0 else -1
@@ -173,9 +172,11 @@ def run_trials_batched(jobs, per_batch, work_dir, train_config, verbose, data_fi
         refused = None
         try:
             metrics = train_trials_batched(trainers)
-        except (_lib.HipCallError, ValueError) as exc:
-            # a step of this configuration meets a kernel without the batched form (a per-layer fallback, an unusual
-            # shape): `trial_mode: batched` says so; `auto` trains the group in threads instead, from the start
+        except BatchingRefused as exc:
+            # the first step of this configuration meets a kernel without the batched form (the per-layer conv kernels
+            # of `fused_blocks: false`): `trial_mode: batched` says so; `auto` trains the group in threads instead, from
+            # the start.  Anything else -- another HIP error, the reference's ValueError on a one-row last batch --
+            # is the training's own failure and propagates in both modes
             if not auto:
                 raise
             refused = exc
@@ -185,12 +186,14 @@ def run_trials_batched(jobs, per_batch, work_dir, train_config, verbose, data_fi
             for t in trainers:
                 t.engine.release()
         if refused is not None:
-            logging.getLogger("Main").warning(f"trial_mode auto: batched launches refused ({refused}); trials "
-                                              f"{[k + 1 for k in group]} run in threads")
-            for lg in loggers:
+            logging.getLogger("Main").warning(f"trial_mode auto: batched launches refused (kernel {refused.kernel}); "
+                                              f"trials {[k + 1 for k in group]} run in threads")
+            for k, lg in zip(group, loggers):
                 for h in list(lg.handlers):
                     h.close()
                     lg.removeHandler(h)
+                for name in ("messages.txt", "losses.csv"):      # the threaded rerun starts the trial's logs afresh
+                    open(os.path.join(f"{work_dir}/training/job_{k + 1}", name), "w").close()
             del trainers
             out += run_trials_threaded(group, min(4, len(group)), work_dir, plain_config, verbose, data_file, timeout, trial_seed)
             continue
@@ -220,24 +223,51 @@ def run_trials_threaded(jobs, threads, work_dir, train_config, verbose, data_fil
         return list(ex.map(one, jobs))
 
 
+def batched_tile_rows_mult(batch_size):
+    """``tile_rows_mult`` of ``trial_mode: batched`` for the conv networks (where the configuration leaves it unset).
+    Below ``RAAE_BIG_ROWS`` (1024) rows 4: every trial's launches sized as its share of a 4x larger batch
+    (raae_tile_hint; +33 % at 8 trials of 256 rows, +48 % at 16).  From 1024 rows on 1: there the launches already
+    have the sample groups that 4 gives at 256 rows, and a batched trial is then bit for bit the same trial run under
+    ``trial_mode: threads`` (tile_rows_mult 1 too), so ``auto`` choosing either changes no result.  Keyed on the mode
+    and the batch size, never on the group size: a trial's result is the same whatever runs beside it."""
+    return 4 if int(batch_size) < 1024 else 1
+
+
+# `auto` keeps the conv networks' trials in threads from this batch size up.  None: batched wins at every size measured.
+# 8 conv trials on one MI355X, aggregate steps/s, batched against 8 engines on their own streams (DESIGN.md section 9):
+# 1024 rows 1004 / 929 (1.08x), 2048 rows 620 / 404 (1.54x), 4096 rows 393 / 283 (1.39x).
+AUTO_THREADS_FROM_ROWS = None
+
+
+def choose_trial_mode(cfg):
+    """The trial mode ``run_trials`` uses for the configuration ``cfg`` (a ``Parameters`` or a dict):
+    ``"batched"``, ``"threads"`` or ``"processes"``.  ``trial_mode: auto`` picks ``batched`` where the trials can be
+    batched (``rng_mode: philox``, ``precision: fp32``, the fused step head and discriminator; for the conv networks up
+    to ``AUTO_THREADS_FROM_ROWS``), ``threads`` otherwise; ``batched`` on a configuration that cannot be batched
+    raises ``ValueError``."""
+    mode = str(cfg.get("trial_mode", "auto"))
+    if mode not in ("auto", "batched", "threads", "processes"):
+        raise ValueError(f"trial_mode must be 'auto', 'batched', 'threads' or 'processes', not {mode!r}")
+    can_batch = (cfg.get("rng_mode", "philox") == "philox" and cfg.get("precision", "fp32") == "fp32" and
+                 bool(cfg.get("fused_step_begin", True)) and bool(cfg.get("fused_discriminator", True)))
+    if mode == "batched" and not can_batch:
+        raise ValueError("trial_mode: batched needs rng_mode: philox, precision: fp32, fused_step_begin and "
+                         "fused_discriminator (use trial_mode: threads)")
+    if mode != "auto":
+        return mode
+    dense = cfg.get("ae_form", None) == "FC"
+    wins = dense or AUTO_THREADS_FROM_ROWS is None or int(cfg.get("batch_size", 0)) < AUTO_THREADS_FROM_ROWS
+    return "batched" if can_batch and wins else "threads"
+
+
 def run_trials(trials, work_dir, train_config, verbose, data_file, timeout, logger):
     """All trials; returns ``[(metrics, time_used)]`` in trial order and the number of worker processes."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     nworkers = 1
-    mode = str(train_config.get("trial_mode", "auto"))
-    if mode not in ("auto", "batched", "threads", "processes"):
-        raise ValueError(f"trial_mode must be 'auto', 'batched', 'threads' or 'processes', not {mode!r}")
     philox = train_config.get("rng_mode", "philox") == "philox"
-    dense = train_config.get("ae_form", None) == "FC"
-    can_batch = (philox and train_config.get("precision", "fp32") == "fp32" and
-                 train_config.get("fused_step_begin", True) and train_config.get("fused_discriminator", True) and
-                 (dense or int(train_config.get("batch_size", 0)) < 1024))
-    if mode == "batched" and not can_batch:
-        raise ValueError("trial_mode: batched needs rng_mode: philox, precision: fp32 and, for the conv networks, "
-                         "batch_size < 1024 (the large-batch conv kernels have no batched form: use trial_mode: threads)")
-    auto = mode == "auto"
-    if auto:                # one launch sequence for all trials of a group where the step's kernels have the batched form
-        mode = "batched" if can_batch else "threads"
+    auto = str(train_config.get("trial_mode", "auto")) == "auto"
+    # one launch sequence for all trials of a group where the step's kernels have the batched form
+    mode = choose_trial_mode(train_config)
     batched = (2 if auto else 1) if mode == "batched" else 0
     if batched:
         mode = "threads"          # same process / seed plumbing below; the worker trains its group in lockstep instead

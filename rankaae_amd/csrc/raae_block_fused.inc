@@ -467,13 +467,14 @@ __global__ __launch_bounds__(256) void block_fwd_a_kernel(BlockFwdAArgs ka) {
     const BlockFwdAArgs& a = raae::args_to_lds(&sa);
     block_fwd_a_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }
-// one trial per grid plane (raae_common.h, "batched launches over independent trials"): the launch-bound instances only
-template <int KIND>
+// one trial per grid plane (raae_common.h, "batched launches over independent trials"): the same body as the
+// single-trial instance of the same <KIND, BIG>, the launch-bound and the large-batch instances alike
+template <int KIND, bool BIG = false>
 __global__ __launch_bounds__(256) void block_fwd_a_kernel_m(const BlockFwdAArgs* table) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ BlockFwdAArgs sa;
     const BlockFwdAArgs& a = raae::args_from_table(&sa, table);
-    block_fwd_a_body<KIND, false>(a, blockIdx.x, gridDim.x, dyn);
+    block_fwd_a_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }
 
 typedef raae_block_fwd_b_t BlockFwdBArgs;
@@ -668,12 +669,12 @@ __global__ __launch_bounds__(256) void block_fwd_b_kernel(BlockFwdBArgs ka) {
     const BlockFwdBArgs& a = raae::args_to_lds(&sa);
     block_fwd_b_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }
-template <int KIND>
+template <int KIND, bool BIG = false>
 __global__ __launch_bounds__(256) void block_fwd_b_kernel_m(const BlockFwdBArgs* table) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ BlockFwdBArgs sa;
     const BlockFwdBArgs& a = raae::args_from_table(&sa, table);
-    block_fwd_b_body<KIND, false>(a, blockIdx.x, gridDim.x, dyn);
+    block_fwd_b_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }
 
 // =====================================================================================
@@ -1087,12 +1088,12 @@ __global__ __launch_bounds__(256) void block_bwd_b_kernel(BlockBwdBArgs ka) {
     const BlockBwdBArgs& a = raae::args_to_lds(&sa);
     block_bwd_b_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }
-template <int KIND>
+template <int KIND, bool BIG = false>
 __global__ __launch_bounds__(256) void block_bwd_b_kernel_m(const BlockBwdBArgs* table) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ BlockBwdBArgs sa;
     const BlockBwdBArgs& a = raae::args_from_table(&sa, table);
-    block_bwd_b_body<KIND, false>(a, blockIdx.x, gridDim.x, dyn);
+    block_bwd_b_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }
 
 typedef raae_block_bwd_a_t BlockBwdAArgs;
@@ -1497,10 +1498,10 @@ __global__ __launch_bounds__(256) void block_bwd_a_kernel(BlockBwdAArgs ka) {
     const BlockBwdAArgs& a = raae::args_to_lds(&sa);
     block_bwd_a_body<KIND, BIG>(a, dyn);
 }
-template <int KIND>
+template <int KIND, bool BIG = false>
 __global__ __launch_bounds__(256) void block_bwd_a_kernel_m(const BlockBwdAArgs* table) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ BlockBwdAArgs sa;
     const BlockBwdAArgs& a = raae::args_from_table(&sa, table);
-    block_bwd_a_body<KIND, false>(a, dyn);
+    block_bwd_a_body<KIND, BIG>(a, dyn);
 }

@@ -787,20 +787,15 @@ static bool use_big(int B, int kind, int family) {
 }
 // ---- shape-specialised instances of the fused block kernels (raae_block_shapes.inc)
 // (`big`: the instance for batches of >= 1024 rows, which carries the 16-byte staging / elementwise paths)
-// (the launch-bound instances go through raae::launch: they have the batched form KERNEL_m, one trial per grid plane; the
-// large-batch instances do not -- a recording that meets one is refused, raae::record_unsupported)
-#define RAAE_LAUNCH_KIND_BIG(KERNEL, ...) if (big) switch (kind) { \
-        case 0: RAAE_PLAIN_LAUNCH((KERNEL<0, true>), __VA_ARGS__); break; case 1: RAAE_PLAIN_LAUNCH((KERNEL<1, true>), __VA_ARGS__); break; \
-        case 2: RAAE_PLAIN_LAUNCH((KERNEL<2, true>), __VA_ARGS__); break; case 3: RAAE_PLAIN_LAUNCH((KERNEL<3, true>), __VA_ARGS__); break; \
-        case 4: RAAE_PLAIN_LAUNCH((KERNEL<4, true>), __VA_ARGS__); break; case 5: RAAE_PLAIN_LAUNCH((KERNEL<5, true>), __VA_ARGS__); break; \
-        case 6: RAAE_PLAIN_LAUNCH((KERNEL<6, true>), __VA_ARGS__); break; default: RAAE_PLAIN_LAUNCH((KERNEL<-1, true>), __VA_ARGS__); } \
-    else RAAE_LAUNCH_KIND(KERNEL, __VA_ARGS__)
-#define RAAE_LAUNCH_KIND(KERNEL, ...) switch (kind) { \
-        case 0: raae::launch(KERNEL<0, false>, KERNEL##_m<0>, __VA_ARGS__); break; case 1: raae::launch(KERNEL<1, false>, KERNEL##_m<1>, __VA_ARGS__); break; \
-        case 2: raae::launch(KERNEL<2, false>, KERNEL##_m<2>, __VA_ARGS__); break; case 3: raae::launch(KERNEL<3, false>, KERNEL##_m<3>, __VA_ARGS__); break; \
-        case 4: raae::launch(KERNEL<4, false>, KERNEL##_m<4>, __VA_ARGS__); break; case 5: raae::launch(KERNEL<5, false>, KERNEL##_m<5>, __VA_ARGS__); break; \
-        case 6: raae::launch(KERNEL<6, false>, KERNEL##_m<6>, __VA_ARGS__); break; default: raae::launch(KERNEL<-1, false>, KERNEL##_m<-1>, __VA_ARGS__); }
-static_assert(kNumBlkShapes == 7, "RAAE_LAUNCH_KIND enumerates the shape table");
+// (every instance goes through raae::launch: each has the batched form KERNEL_m<KIND, BIG>, one trial per grid plane)
+#define RAAE_LAUNCH_KIND_AS(KERNEL, BIG_, ...) switch (kind) { \
+        case 0: raae::launch(KERNEL<0, BIG_>, KERNEL##_m<0, BIG_>, __VA_ARGS__); break; case 1: raae::launch(KERNEL<1, BIG_>, KERNEL##_m<1, BIG_>, __VA_ARGS__); break; \
+        case 2: raae::launch(KERNEL<2, BIG_>, KERNEL##_m<2, BIG_>, __VA_ARGS__); break; case 3: raae::launch(KERNEL<3, BIG_>, KERNEL##_m<3, BIG_>, __VA_ARGS__); break; \
+        case 4: raae::launch(KERNEL<4, BIG_>, KERNEL##_m<4, BIG_>, __VA_ARGS__); break; case 5: raae::launch(KERNEL<5, BIG_>, KERNEL##_m<5, BIG_>, __VA_ARGS__); break; \
+        case 6: raae::launch(KERNEL<6, BIG_>, KERNEL##_m<6, BIG_>, __VA_ARGS__); break; default: raae::launch(KERNEL<-1, BIG_>, KERNEL##_m<-1, BIG_>, __VA_ARGS__); }
+#define RAAE_LAUNCH_KIND_BIG(KERNEL, ...) if (big) { RAAE_LAUNCH_KIND_AS(KERNEL, true, __VA_ARGS__) } \
+    else { RAAE_LAUNCH_KIND_AS(KERNEL, false, __VA_ARGS__) }
+static_assert(kNumBlkShapes == 7, "RAAE_LAUNCH_KIND_AS enumerates the shape table");
 static bool same_conv(const raae_conv_t& x, const raae_conv_t& y) { return !memcmp(&x, &y, sizeof(raae_conv_t)); }
 // phase A kernels see (Cin, Cout, Lin, L1, Lout, E, cv1, cvs); phase B kernels (Cin, Cout, L1, Lout, cv2, cve)
 static int blk_kind_a(int Cin, int Cout, int Lin, int L1, int Lout, int E, const raae_conv_t& cv1, int has_short,

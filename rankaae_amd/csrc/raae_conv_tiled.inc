@@ -959,12 +959,12 @@ __global__ __launch_bounds__(256) void wgrad_multi_kernel(WgradMultiArgs km) {
     const WgradMultiArgs& m = raae::args_to_lds(&sm);
     wgrad_multi_body<KIND, BIG>(m, blockIdx.x, dyn);
 }
-template <int KIND>
+template <int KIND, bool BIG = false>
 __global__ __launch_bounds__(256) void wgrad_multi_kernel_m(const WgradMultiArgs* table) {     // one trial per grid plane
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ WgradMultiArgs sm;
     const WgradMultiArgs& m = raae::args_from_table(&sm, table);
-    wgrad_multi_body<KIND, false>(m, blockIdx.x, dyn);
+    wgrad_multi_body<KIND, BIG>(m, blockIdx.x, dyn);
 }
 
 // ------------------------------------------------------------------ grad materialise (sliced)

@@ -517,38 +517,54 @@ extern "C" int raae_slab_reduce(const float* g_slabs, long slab_stride, const un
 
 
 // ---------------------------------------------------------------- batched launches over trials (raae_common.h)
+#include <cstdio>
+#include <string>
 #include <vector>
 namespace {
 struct LaunchRec { const void* fn; dim3 grid, block; unsigned lds, nbytes; unsigned char args[4096]; };
-struct Recording { std::vector<LaunchRec> recs; bool bad = false; };
+struct Recording { std::vector<LaunchRec> recs; bool bad = false; std::string refused; };
 thread_local Recording* g_recording = nullptr;
+thread_local std::string g_refusal;      // why this thread's last recording or program build was refused
 struct MultiProgram { std::vector<LaunchRec> recs; std::vector<size_t> off; unsigned char* table = nullptr; int T = 0; };
+void refuse(Recording* r, const std::string& why) {
+    if (!r->bad) r->refused = why;       // the first offending launch
+    r->bad = true;
+}
 }  // namespace
 void raae::record_launch(const void* multi_fn, dim3 grid, dim3 block, size_t lds, const void* args, size_t nbytes) {
     Recording* r = g_recording;
     if (!r) return;
     LaunchRec rec;
-    if (nbytes > sizeof(rec.args) || grid.z != 1) { r->bad = true; return; }
+    if (nbytes > sizeof(rec.args) || grid.z != 1) {
+        refuse(r, "launch " + std::to_string(r->recs.size()) + ": " + std::to_string(nbytes) + "-byte argument block or a 3-D grid");
+        return;
+    }
     rec.fn = multi_fn; rec.grid = grid; rec.block = block; rec.lds = (unsigned)lds; rec.nbytes = (unsigned)nbytes;
     memcpy(rec.args, args, nbytes);
     r->recs.push_back(rec);
 }
-void raae::record_unsupported() {
-    if (g_recording) g_recording->bad = true;
+void raae::record_unsupported(const char* kernel) {
+    if (g_recording) refuse(g_recording, kernel);
 }
 extern "C" int raae_record_begin(void) {
     if (g_recording) return RAAE_EINVAL;
     g_recording = new Recording();
+    g_refusal.clear();
     return 0;
 }
 extern "C" int raae_record_end(void** handle, int* n_launches) {
     RAAE_CHECK_ARG(handle && g_recording);
     Recording* r = g_recording;
     g_recording = nullptr;
-    if (r->bad) { delete r; return RAAE_EINVAL; }
+    if (r->bad) { g_refusal = r->refused; delete r; return RAAE_EINVAL; }
     if (n_launches) *n_launches = (int)r->recs.size();
     *handle = r;
     return 0;
+}
+extern "C" int raae_record_refusal(char* buf, int n) {
+    RAAE_CHECK_ARG(buf && n > 0);
+    snprintf(buf, (size_t)n, "%s", g_refusal.c_str());
+    return (int)g_refusal.size();
 }
 extern "C" int raae_record_free(void* handle) { delete (Recording*)handle; return 0; }
 extern "C" int raae_multi_build(void* const* handles, int T, void** program) {
@@ -565,12 +581,22 @@ extern "C" int raae_multi_build(void* const* handles, int T, void** program) {
     std::vector<unsigned char> host(total, 0);
     for (int t = 0; t < T; ++t) {
         const Recording* r = (const Recording*)handles[t];
-        if (!r || r->recs.size() != r0->recs.size()) { delete mp; return RAAE_EINVAL; }
+        if (!r || r->recs.size() != r0->recs.size()) {
+            g_refusal = "trial " + std::to_string(t) + " logged " + std::to_string(r ? r->recs.size() : 0) +
+                        " launches, trial 0 " + std::to_string(r0->recs.size());
+            delete mp;
+            return RAAE_EINVAL;
+        }
         for (size_t i = 0; i < r->recs.size(); ++i) {
             const LaunchRec &a = r0->recs[i], &b = r->recs[i];
             // the trials must be structurally identical: same kernel instance, geometry and LDS at every launch
             if (a.fn != b.fn || a.grid.x != b.grid.x || a.grid.y != b.grid.y || a.block.x != b.block.x || a.lds != b.lds ||
-                a.nbytes != b.nbytes) { delete mp; return RAAE_EINVAL; }
+                a.nbytes != b.nbytes) {
+                g_refusal = "launch " + std::to_string(i) + " of trial " + std::to_string(t) +
+                            " differs from trial 0's in kernel instance, geometry or LDS";
+                delete mp;
+                return RAAE_EINVAL;
+            }
             memcpy(host.data() + mp->off[i] + (size_t)t * a.nbytes, b.args, a.nbytes);
         }
     }

@@ -6,13 +6,18 @@ dense networks launches ~100 kernels of 16-64 workgroups each: one trial leaves 
 of concurrent trials saturate at the four hardware queues (2.8-3.5x).  A ``TrialBatch`` steps T engines with ONE
 launch sequence: every kernel of the step runs once with ``gridDim.z = T``, plane z working on trial z's buffers
 (``include/rankaae_hip.h``: raae_record_* / raae_multi_*).  Each trial's arithmetic is the kernel body it runs alone:
-its weights are bit for bit those of the same trial stepped by itself (tests/test_engine_gpu.py).
+its weights are bit for bit those of the same trial stepped by itself (tests/test_engine_gpu.py,
+tests/test_trial_batch_large_gpu.py).
 
 The first step of every batch shape is run by each engine on its own (eagerly: that is where an engine records its
 gradient-slab tables) while the library logs its launches; from the second step on the batch replays one captured
-hipGraph.  All engines of a batch share one HIP stream.  Supported: both networks at batches below 1024 rows (the
-launch-bound kernel instances have the batched form; a step that meets a large-batch instance or a per-layer kernel is
-refused with an error, never run partially), ``rng_mode: philox``, fp32, one GPU.
+hipGraph.  All engines of a batch share one HIP stream; an engine's side-stream branches (conv networks from
+``overlap_min_batch`` rows) are replayed in the order they were issued, on that one stream.  Supported: both networks
+at every batch size -- the conv networks' fused-block kernels have the batched form in their launch-bound and their
+large-batch (``RAAE_BIG_ROWS``) instances alike -- ``rng_mode: philox``, fp32, one GPU.  A step that meets a kernel
+without the batched form (the per-layer conv kernels of ``fused_blocks: false``) is refused on its first step with
+``BatchingRefused``, which names that kernel; nothing runs partially.  The per-epoch validation is batched the same way;
+a validation whose recording is refused runs the trials' validations one after the other inside the batch's graph.
 """
 import ctypes as C
 
@@ -20,6 +25,25 @@ import torch
 
 from . import _lib, ops
 from ._lib import check
+
+
+class BatchingRefused(_lib.HipCallError):
+    """The recorder refused the first step of a batch shape: a launch of the step has no batched form, or the
+    trials' launch sequences differ.  ``kernel``: the refused kernel's name (or which launch differed)."""
+
+    def __init__(self, what, kernel):
+        super().__init__(f"{what}: {kernel}")
+        self.kernel = kernel
+
+
+_EINVAL = -1        # RAAE_EINVAL: what the recorder returns when it refuses
+
+
+def _refusal(lib):
+    """Why the calling thread's last raae_record_end / raae_multi_build refused (raae_record_refusal)."""
+    buf = C.create_string_buffer(256)
+    lib.raae_record_refusal(buf, len(buf))
+    return buf.value.decode() or "?"
 
 
 class TrialBatch:
@@ -61,16 +85,23 @@ class TrialBatch:
                     finally:
                         h, n = C.c_void_p(), C.c_int(0)
                         rc = lib.raae_record_end(C.byref(h), C.byref(n))
-                    check(rc, "raae_record_end (a launch of the step has no batched form)")
+                    if rc != 0:
+                        why = _refusal(lib)
+                        for h_ in handles[:t]:
+                            lib.raae_record_free(C.c_void_p(h_))
+                        raise BatchingRefused("raae_record_end (a launch of the step has no batched form)", why)
                     P.graphs[bool(smooth)] = None
                     handles[t] = h
                     counts.append(n.value)
                 torch.cuda.synchronize(self.engines[0].device)
                 prog = C.c_void_p()
                 rc = lib.raae_multi_build(handles, self.T, C.byref(prog))
+                why = _refusal(lib) if rc != 0 else None
                 for h in handles:
                     lib.raae_record_free(C.c_void_p(h))
-                check(rc, f"raae_multi_build (the trials' steps differ: {counts} launches)")
+                if rc == _EINVAL:
+                    raise BatchingRefused(f"raae_multi_build (the trials' steps differ: {counts} launches)", why)
+                check(rc, "raae_multi_build")
                 self.programs[key] = [prog, None]
                 return
             prog, graph = self.programs[key]
@@ -105,9 +136,9 @@ class TrialBatch:
                             if rc == 0:
                                 handles.append(h)
                             else:
-                                # a validation split of >= 1024 rows meets the conv networks' large-batch kernel
-                                # instances, which have no batched form: the trials' validations then run one after the
-                                # other on the shared stream (still one captured graph, and still on the device)
+                                # a validation that meets a kernel without the batched form (the per-layer conv kernels
+                                # of `fused_blocks: false`): the trials' validations then run one after the other on
+                                # the shared stream (still one captured graph, and still on the device)
                                 batched = False
                 torch.cuda.synchronize(self.engines[0].device)
                 prog = None
