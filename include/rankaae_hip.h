@@ -264,6 +264,20 @@ int raae_gather_batch(const float* spec, const float* aux, const long* idx, cons
  *   summed by 8 lanes instead of one thread; the result does not depend on it beyond summation order). */
 int raae_adam_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride, const unsigned short* seg_nslab,
                    long n, const double* hyper, const int* step, int decoupled, int max_nslab, void* stream);
+
+/* Update rules of raae_optim_step (config key `optimizer_name`). */
+#define RAAE_OPT_ADAM 0       /* torch.optim.Adam  (raae_adam_step, decoupled = 0) */
+#define RAAE_OPT_ADAMW 1      /* torch.optim.AdamW (raae_adam_step, decoupled = 1) */
+#define RAAE_OPT_RADAM 2      /* torch_optimizer.RAdam 0.1.0: rectified Adam, decoupled weight decay */
+#define RAAE_OPT_ADABOUND 3   /* torch_optimizer.AdaBound 0.1.0 (amsbound = False): Adam with clamped steps, L2 decay */
+/* Fused multi-tensor update of any of the four rules, same arena / slab / step conventions as raae_adam_step
+ * (the Adam rules launch exactly its kernels).
+ *   hyper (device, 8 doubles): {lr, beta1, beta2, eps, weight_decay, base_lr, final_lr, gamma}; the Adam rules
+ *   read the first five, RAdam the first five, AdaBound all eight (base_lr: the lr at construction, final_lr 0.1,
+ *   gamma 1e-3).  The per-step scalars are formed in double from hyper and *step inside the kernel, so an lr
+ *   written into hyper between graph replays takes effect. */
+int raae_optim_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride, const unsigned short* seg_nslab,
+                    long n, int rule, const double* hyper, const int* step, int max_nslab, void* stream);
 /* ====================== 1-D convolutional networks (ae_form: compact) ======================
  * Activations are [B][C][L] fp32, stored RAW (pre-activation); what a consumer sees is a *view*:
  *     value = mask * BatchNorm( PReLU(raw, slope_c) )          (each stage optional)
@@ -532,7 +546,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 17
+#define RAAE_ABI_VERSION 18
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -1,4 +1,4 @@
-// Fused multi-tensor Adam/AdamW over the flat parameter arena, the per-step tick,
+// Fused multi-tensor Adam/AdamW, RAdam and AdaBound over the flat parameter arena, the per-step tick,
 // the Philox random tape, and HIP stream/graph/event plumbing.
 #include "raae_common.h"
 #include <string.h>
@@ -129,6 +129,175 @@ __global__ __launch_bounds__(256) void adam_wide_kernel(AdamArgs a) {
 __global__ __launch_bounds__(256) void adam_wide_kernel_m(const AdamArgs* t) {
     const AdamArgs a = t[blockIdx.z];
     adam_wide_body(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled);
+}
+
+// ---- RAdam and AdaBound (torch_optimizer 0.1.0, the optimizer_name values the reference takes from that package) ----
+// One kernel instance per rule: OptRule<R>::scalars forms the per-step scalars in double (Python floats) from the
+// device hyper block and step count, in the operation order of the Python source (no contraction into fma there);
+// OptRule<R>::update is the per-element fp32 update in the order of the torch ops.  Gradient reading as in Adam.
+constexpr int OPT_NSC = 10;
+struct OptimArgs { float* p; float* m; float* v; const float* g_slabs; long slab_stride; const unsigned short* seg_nslab;
+                   long n; const double* hyper; const int* step; };
+template <int RULE> struct OptRule;
+
+// torch_optimizer.RAdam.step.  The class caches (t, N, step size) in a 10-entry buffer keyed on t % 10, filled by the
+// first tensor stepped at a given t; every tensor of one optimizer here shares one step count, so the cache always
+// holds what the formula gives at the current lr, and the formula is evaluated directly.  N is formed in double in
+// this order: at t = 5 it misses 5 by only 4e-3 (beta2 = 0.999) or 4e-4 (0.9999); t = 6 is the first rectified step.
+template <> struct OptRule<RAAE_OPT_RADAM> {
+    __device__ static void scalars(const double* h, int step, float* s) {
+#pragma clang fp contract(off)
+        const double lr = h[0], b1 = h[1], b2 = h[2], eps = h[3], wd = h[4];
+        const double t = (double)step;
+        const double b2t = pow(b2, t);
+        const double nmax = 2.0 / (1.0 - b2) - 1.0;
+        const double nsma = nmax - 2.0 * t * b2t / (1.0 - b2t);
+        const bool rect = nsma >= 5.0;
+        const double ss = rect ? lr * sqrt((1.0 - b2t) * (nsma - 4.0) / (nmax - 4.0) * (nsma - 2.0) / nsma * nmax /
+                                           (nmax - 2.0)) / (1.0 - pow(b1, t))
+                               : lr / (1.0 - pow(b1, t));
+        s[0] = (float)b1;
+        s[1] = (float)(1.0 - b1);
+        s[2] = (float)b2;
+        s[3] = (float)(1.0 - b2);
+        s[4] = (float)(-ss);
+        s[5] = (float)eps;
+        s[6] = (float)(-wd * lr);           // decoupled decay: p.add_(p, alpha=-wd*lr)
+        s[7] = wd != 0.0 ? 1.f : 0.f;
+        s[8] = rect ? 1.f : 0.f;
+        s[9] = 0.f;
+    }
+    __device__ static void update(const float (&s)[OPT_NSC], float& p, float& m, float& v, float g) {
+        v = v * s[2];
+        v = v + (s[3] * g) * g;             // exp_avg_sq.mul_(b2).addcmul_(g, g, value=1-b2), before exp_avg
+        m = m * s[0];
+        m = m + s[1] * g;                   // exp_avg.mul_(b1).add_(g, alpha=1-b1)
+        if (s[7] != 0.f) p = p + s[6] * p;
+        if (s[8] != 0.f) p = p + (s[4] * m) / (sqrtf(v) + s[5]);   // addcdiv_(exp_avg, sqrt(v) + eps, value=-ss)
+        else p = p + s[4] * m;                                     // the first steps: SGD with momentum
+    }
+};
+
+// torch_optimizer.AdaBound.step (amsbound = False).  hyper[5] = base_lr (the lr at construction, self.base_lrs; a
+// ReduceLROnPlateau cut of hyper[0] moves the bounds through final_lr * lr / base_lr).
+template <> struct OptRule<RAAE_OPT_ADABOUND> {
+    __device__ static void scalars(const double* h, int step, float* s) {
+#pragma clang fp contract(off)
+        const double lr = h[0], b1 = h[1], b2 = h[2], eps = h[3], wd = h[4], base_lr = h[5], final_lr = h[6],
+                     gamma = h[7];
+        const double t = (double)step;
+        const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
+        const double ss = lr * sqrt(bc2) / bc1;
+        const double flr = final_lr * lr / base_lr;
+        s[0] = (float)b1;
+        s[1] = (float)(1.0 - b1);
+        s[2] = (float)b2;
+        s[3] = (float)(1.0 - b2);
+        s[4] = (float)ss;                                       // torch.full_like(denom, step_size)
+        s[5] = (float)(flr * (1.0 - 1.0 / (gamma * t + 1.0)));  // clamp_ bounds, as fp32 scalars
+        s[6] = (float)(flr * (1.0 + 1.0 / (gamma * t)));
+        s[7] = (float)eps;
+        s[8] = (float)wd;
+        s[9] = wd != 0.0 ? 1.f : 0.f;
+    }
+    __device__ static void update(const float (&s)[OPT_NSC], float& p, float& m, float& v, float g) {
+        if (s[9] != 0.f) g = g + s[8] * p;                 // grad.add(p, alpha=wd): coupled L2
+        m = m * s[0];
+        m = m + s[1] * g;
+        v = v * s[2];
+        v = v + (s[3] * g) * g;
+        float x = s[4] / (sqrtf(v) + s[7]);                // step_size.div_(denom).clamp_(lo, hi).mul_(exp_avg)
+        x = x < s[5] ? s[5] : (x > s[6] ? s[6] : x);       // (NaN passes through, as in torch.clamp)
+        x = x * m;
+        p = p + (-x);
+    }
+};
+
+template <int RULE>
+__device__ __forceinline__ void optim_scalars(const OptimArgs& a, float (&sc)[OPT_NSC]) {
+    __shared__ float s_sc[OPT_NSC];
+    if (threadIdx.x == 0) OptRule<RULE>::scalars(a.hyper, a.step[0], s_sc);
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < OPT_NSC; ++k) sc[k] = s_sc[k];
+}
+
+template <int RULE>
+__device__ __forceinline__ void optim_body(const OptimArgs& a) {
+    float sc[OPT_NSC];
+    optim_scalars<RULE>(a, sc);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
+        const int ns = a.seg_nslab[i >> 6];
+        if (ns == 0) continue;
+        float g = 0.f;                                  // adam_body's fixed-order slab sum
+        int s = 0;
+        for (; s + 8 <= ns; s += 8) {
+            float t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t[u] = a.g_slabs[(size_t)(s + u) * a.slab_stride + i];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) g += t[u];
+        }
+        for (; s < ns; ++s) g += a.g_slabs[(size_t)s * a.slab_stride + i];
+        float pv = a.p[i], mv = a.m[i], vv = a.v[i];
+        OptRule<RULE>::update(sc, pv, mv, vv, g);
+        a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
+    }
+}
+
+template <int RULE>
+__device__ __forceinline__ void optim_wide_body(const OptimArgs& a) {
+    float sc[OPT_NSC];
+    optim_scalars<RULE>(a, sc);
+    const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;   // adam_wide_body's lane split and shuffle tree
+    const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+    for (long base = wave0; base < a.n; base += (long)gridDim.x * 32) {
+        const long i = base + el;                       // n is a multiple of 64: i < n whenever base < n
+        const int ns = a.seg_nslab[i >> 6];
+        if (ns == 0) continue;                          // uniform over the wave (8 elements share a segment)
+        float g = 0.f;
+        for (int s = ch; s < ns; s += 64) {
+            float t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int r = s + 8 * u;
+                t[u] = a.g_slabs[(size_t)(r < ns ? r : ch) * a.slab_stride + i];
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) g += (s + 8 * u < ns) ? t[u] : 0.f;
+        }
+        g += __shfl_xor(g, 8, 64);
+        g += __shfl_xor(g, 16, 64);
+        g += __shfl_xor(g, 32, 64);
+        if (ch != 0) continue;
+        float pv = a.p[i], mv = a.m[i], vv = a.v[i];
+        OptRule<RULE>::update(sc, pv, mv, vv, g);
+        a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
+    }
+}
+
+template <int RULE> __global__ __launch_bounds__(256) void optim_kernel(OptimArgs a) { optim_body<RULE>(a); }
+template <int RULE> __global__ __launch_bounds__(256) void optim_kernel_m(const OptimArgs* t) {
+    const OptimArgs a = t[blockIdx.z];
+    optim_body<RULE>(a);
+}
+template <int RULE> __global__ __launch_bounds__(256) void optim_wide_kernel(OptimArgs a) { optim_wide_body<RULE>(a); }
+template <int RULE> __global__ __launch_bounds__(256) void optim_wide_kernel_m(const OptimArgs* t) {
+    const OptimArgs a = t[blockIdx.z];
+    optim_wide_body<RULE>(a);
+}
+
+template <int RULE>
+void launch_optim(const OptimArgs& a, int max_nslab, hipStream_t stream) {
+    if (max_nslab > 16) {
+        long g = (a.n + 31) / 32;               // raae_adam_step's geometry
+        if (g > 4096) g = 4096;
+        raae::launch(optim_wide_kernel<RULE>, optim_wide_kernel_m<RULE>, dim3((int)g), dim3(256), 0, stream, a);
+    } else {
+        long g = (a.n + 255) / 256;
+        if (g > 4096) g = 4096;
+        raae::launch(optim_kernel<RULE>, optim_kernel_m<RULE>, dim3((int)g), dim3(256), 0, stream, a);
+    }
 }
 
 __global__ void tick_kernel(int* steps, int n, unsigned mask, unsigned long long* rng_counter, int* cursor,
@@ -354,6 +523,20 @@ extern "C" int raae_adam_step(float* p, float* m, float* v, const float* g_slabs
         if (g > 4096) g = 4096;
         raae::launch(adam_kernel, adam_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
     }
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_optim_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                               const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
+                               int max_nslab, void* stream) {
+    RAAE_CHECK_ARG(rule >= RAAE_OPT_ADAM && rule <= RAAE_OPT_ADABOUND);
+    if (rule == RAAE_OPT_ADAM || rule == RAAE_OPT_ADAMW)
+        return raae_adam_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, rule == RAAE_OPT_ADAMW,
+                              max_nslab, stream);
+    RAAE_CHECK_ARG(p && m && v && g_slabs && seg_nslab && hyper && step && n > 0 && (n % 64) == 0 && max_nslab >= 0);
+    const OptimArgs a = {p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step};
+    if (rule == RAAE_OPT_RADAM) launch_optim<RAAE_OPT_RADAM>(a, max_nslab, (hipStream_t)stream);
+    else launch_optim<RAAE_OPT_ADABOUND>(a, max_nslab, (hipStream_t)stream);
     RAAE_LAUNCH_RET();
 }
 

@@ -25,6 +25,7 @@ from torch import nn
 
 from . import _lib, ops
 from .metrics import StyleMetrics
+from .parameter import check_optimizer
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -72,19 +73,23 @@ class Arena:
 
 
 class OptState:
-    """One optimizer of ``Trainer.load_optimizers``: a contiguous arena range + moments."""
+    """One optimizer of ``Trainer.load_optimizers``: a contiguous arena range + moments.  ``rule``: ``_lib.OPT_*``;
+    ``base_lr`` (the lr at construction), ``final_lr`` and ``gamma`` are AdaBound's (torch_optimizer 0.1.0 defaults)."""
 
-    def __init__(self, index, name, lo, hi, lr, betas, eps, wd, device):
+    def __init__(self, index, name, lo, hi, lr, betas, eps, wd, device, rule=_lib.OPT_ADAMW, final_lr=0.1, gamma=1e-3):
         self.index, self.name, self.lo, self.hi = index, name, lo, hi
         self.lr, self.betas, self.eps, self.wd = float(lr), betas, float(eps), float(wd)
+        self.rule, self.base_lr, self.final_lr, self.gamma = rule, float(lr), float(final_lr), float(gamma)
         self.m = torch.zeros(hi - lo, device=device)
         self.v = torch.zeros(hi - lo, device=device)
-        self.hyper = torch.zeros(5, dtype=torch.float64, device=device)
+        # {lr, beta1, beta2, eps, weight_decay, base_lr, final_lr, gamma}: the Adam rules read the first five; only lr
+        # changes after construction (PlateauScheduler), base_lr stays what it was (AdaBound's self.base_lrs)
+        self.hyper = torch.zeros(8, dtype=torch.float64, device=device)
         self.push()
 
     def push(self):
-        self.hyper.copy_(torch.tensor([self.lr, self.betas[0], self.betas[1], self.eps, self.wd],
-                                      dtype=torch.float64))
+        self.hyper.copy_(torch.tensor([self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.base_lr,
+                                       self.final_lr, self.gamma], dtype=torch.float64))
 
 
 # ------------------------------------------------------------------------------ tape
@@ -634,8 +639,12 @@ class StepEngine:
     # -- optimizers: trainer.py:333-397 (only the five that ever step under gradient reversal)
     def _make_optimizers(self):
         c, r = self.cfg, self.arena.ranges
+        check_optimizer(c)
         lr = c["lr_base"]
-        self.decoupled = {"AdamW": True, "Adam": False}[c["optimizer_name"]]
+        self.rule = {"Adam": _lib.OPT_ADAM, "AdamW": _lib.OPT_ADAMW, "RAdam": _lib.OPT_RADAM,
+                     "AdaBound": _lib.OPT_ADABOUND}[c["optimizer_name"]]
+        self.decoupled = self.rule == _lib.OPT_ADAMW
+        # the class default where the reference passes no weight_decay: AdamW 0.01; Adam, RAdam and AdaBound 0
         default_wd = 0.01 if self.decoupled else 0.0
         betas_d = (c["dis_beta"] * 0.9, c["dis_beta"] * 0.009 + 0.99)
         spec = [("adversarial", r["disc"][0], r["enc"][1], c["lr_ratio_dis"] * lr, betas_d, default_wd),
@@ -643,7 +652,8 @@ class StepEngine:
                 ("reconstruction", r["enc"][0], r["dec"][1], c["lr_ratio_Reconn"] * lr, (0.9, 0.999), c["weight_decay"]),
                 ("mutual_info", r["enc"][0], r["dec"][1], c["lr_ratio_Mutual"] * lr, (0.9, 0.999), default_wd),
                 ("smoothness", r["dec"][0], r["dec"][1], c["lr_ratio_Smooth"] * lr, (0.9, 0.999), c["weight_decay"])]
-        self.opts = {n: OptState(i, n, lo, hi, l, b, 1e-8, wd, self.device) for i, (n, lo, hi, l, b, wd) in enumerate(spec)}
+        self.opts = {n: OptState(i, n, lo, hi, l, b, 1e-8, wd, self.device, self.rule)
+                     for i, (n, lo, hi, l, b, wd) in enumerate(spec)}
 
     # -- parameter-gradient kernels run on side streams (parallel branches of the captured graph):
     #    they are off the critical path of the data-gradient chain and only Adam needs their slabs.
@@ -895,11 +905,15 @@ class StepEngine:
             # flat gradient -> RCCL mean over ranks -> Adam on the averaged single slab
             ops.slab_reduce(self.G[0, lo:], self.arena.n, P.seg[name][lo // 64:], n, self.G_flat[lo:], P.max_slab[name])
             self._collective(self.G_flat[lo:o.hi])
-            ops.adam_step(self.arena.P[lo:], o.m, o.v, self.G_flat[lo:], self.arena.n, self.seg_ones[lo // 64:], n,
-                          o.hyper, self.steps_dev[o.index:], self.decoupled, 1)
+            g, seg, max_slab = self.G_flat[lo:], self.seg_ones[lo // 64:], 1
         else:
-            ops.adam_step(self.arena.P[lo:], o.m, o.v, self.G[0, lo:], self.arena.n, P.seg[name][lo // 64:], n,
-                          o.hyper, self.steps_dev[o.index:], self.decoupled, P.max_slab[name])
+            g, seg, max_slab = self.G[0, lo:], P.seg[name][lo // 64:], P.max_slab[name]
+        if o.rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW):
+            ops.adam_step(self.arena.P[lo:], o.m, o.v, g, self.arena.n, seg, n, o.hyper, self.steps_dev[o.index:],
+                          self.decoupled, max_slab)
+        else:           # RAdam / AdaBound: raae_optim_step, same arena, slabs and step count
+            ops.optim_step(self.arena.P[lo:], o.m, o.v, g, self.arena.n, seg, n, o.rule, o.hyper,
+                           self.steps_dev[o.index:], max_slab)
         if self.post_phase_hook is not None:  # parity tests: teacher forcing at phase granularity
             self._host_hook(self.post_phase_hook, name, P)
 
@@ -1355,8 +1369,9 @@ class StepEngine:
 
     @_on_stream
     def load_optimizer_state(self, name, params, torch_optimizer):
-        """Copy ``exp_avg`` / ``exp_avg_sq`` / ``step`` of a ``torch.optim.Adam(W)`` whose
-        parameters correspond, in order, to ``params`` (this engine's parameters)."""
+        """Copy ``exp_avg`` / ``exp_avg_sq`` / ``step`` of a ``torch.optim.Adam(W)`` (or an RAdam / AdaBound with the
+        same state keys) whose parameters correspond, in order, to ``params`` (this engine's parameters); an
+        AdaBound's ``base_lrs`` too."""
         o = self.opts[name]
         theirs = [p for grp in torch_optimizer.param_groups for p in grp["params"]]
         assert len(theirs) == len(params)
@@ -1375,6 +1390,8 @@ class StepEngine:
         self.steps_dev[o.index] = step
         for grp in torch_optimizer.param_groups:
             o.lr = float(grp["lr"])
+        if o.rule == _lib.OPT_ADABOUND:
+            o.base_lr = float(torch_optimizer.base_lrs[-1])
         o.push()
 
     def _count_bn_step(self, smooth):

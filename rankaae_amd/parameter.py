@@ -5,9 +5,27 @@ import yaml
 
 from .model import AE_CLS_DICT  # noqa: F401  (re-exported like the reference does)
 
-# optimizers reachable through Trainer.from_data (SURVEY.md finding 4); AdaBound/RAdam need
-# torch_optimizer, which neither the reference's runnable set nor this image provides.
-OPTIM_NAMES = ("Adam", "AdamW")
+# values of the `optimizer_name` key (the reference's OPTIM_DICT, sc/utils/parameter.py:34-39): torch.optim's Adam and
+# AdamW, and AdaBound / RAdam of torch_optimizer 0.1.0 -- all four run as fused HIP updates (rankaae_amd/engine.py)
+OPTIM_NAMES = ("Adam", "AdamW", "AdaBound", "RAdam")
+
+# the learning-rate ratios of the optimizers the reference's load_optimizers builds, in its order (trainer.py:333-387)
+_LR_RATIOS = ("lr_ratio_Reconn", "lr_ratio_Mutual", "lr_ratio_Smooth", "lr_ratio_Corr", "lr_ratio_dis", "lr_ratio_gen")
+
+
+def check_optimizer(cfg):
+    """Refuse a configuration the reference's optimizer classes refuse at construction: an unknown
+    ``optimizer_name``, or for AdaBound / RAdam a learning rate ``lr_ratio_* * lr_base <= 0`` (torch_optimizer raises
+    ``ValueError('Invalid learning rate')``; AdaBound also divides by its initial lr)."""
+    name = cfg.get("optimizer_name")
+    if name not in OPTIM_NAMES:
+        raise ValueError(f"optimizer_name must be one of {OPTIM_NAMES}, not {name!r}")
+    if name in ("AdaBound", "RAdam"):
+        for key in _LR_RATIOS:
+            if key in cfg:
+                lr = cfg[key] * cfg["lr_base"]
+                if not lr > 0.0:
+                    raise ValueError(f"{name}: invalid learning rate {lr!r} ({key} * lr_base); {name} needs lr > 0")
 
 
 class Parameters:

@@ -31,7 +31,7 @@ import torch
 from .dataloader import get_dataloaders
 from .engine import StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
-from .parameter import OPTIM_NAMES, Parameters
+from .parameter import Parameters, check_optimizer
 
 
 def alpha(epoch_percentage, step=800, limit=0.7):
@@ -82,9 +82,8 @@ class Trainer:
         if not self.gradient_reversal or self.use_cnn_discriminator:
             raise ValueError("only gradient_reversal: true with DiscriminatorFC is reachable in the reference "
                              "(SURVEY.md finding 4)")
-        if self.optimizer_name not in OPTIM_NAMES:
-            raise ValueError(f"optimizer_name must be one of {OPTIM_NAMES}")
         cfg = config_parameters.to_dict()
+        check_optimizer(cfg)        # before anything touches the GPU
         self.world, self.rank, self.pg = self._data_parallel_setup(device)
         # one draw from the global generator per trial (also when `seed` is given, so that the generator's state
         # does not depend on the key): trials of one run then use different noise / dropout / latent streams
