@@ -278,6 +278,15 @@ int raae_adam_step(float* p, float* m, float* v, const float* g_slabs, long slab
  *   written into hyper between graph replays takes effect. */
 int raae_optim_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride, const unsigned short* seg_nslab,
                     long n, int rule, const double* hyper, const int* step, int max_nslab, void* stream);
+/* raae_optim_step with a NaN check of the gradient (ABI 19; config key `detect_anomaly`, the reference's
+ * torch.autograd.set_detect_anomaly(True)): the same update, bit for bit, by checked twins of its kernels.
+ *   nan_step (device int, required): 0 while no NaN has been seen.  When an element's gradient -- the fixed-order
+ *   slab sum, before weight decay; elements of 0-slab segments are skipped -- is NaN, *step (the optimizer's
+ *   1-based step count) is written there by compare-and-swap from 0, so it keeps the FIRST step that saw one.  Inf
+ *   is not flagged (anomaly mode checks NaN only; the next step's gradient is NaN).  NULL: RAAE_EINVAL. */
+int raae_optim_step_chk(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                        const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
+                        int max_nslab, int* nan_step, void* stream);
 /* ====================== 1-D convolutional networks (ae_form: compact) ======================
  * Activations are [B][C][L] fp32, stored RAW (pre-activation); what a consumer sees is a *view*:
  *     value = mask * BatchNorm( PReLU(raw, slope_c) )          (each stage optional)
@@ -490,7 +499,7 @@ int raae_step_begin(const raae_step_begin_t* p, void* stream);
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk)) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -546,7 +555,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 18
+#define RAAE_ABI_VERSION 19
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -22,6 +22,7 @@ import argparse
 import logging
 import os
 import signal
+import sys
 import threading
 import time
 
@@ -31,17 +32,29 @@ import torch
 
 from rankaae_amd.logger import create_logger
 from rankaae_amd.parameter import Parameters
-from rankaae_amd.trainer import Trainer
+from rankaae_amd.trainer import AnomalyError, Trainer
 
 
 def timeout_handler(signum, frame):
     raise Exception("Training Overtime!")
 
 
+def log_diverged(logger, exc):
+    """A trial whose training raised ``AnomalyError`` (``detect_anomaly``): the error line in its ``messages.txt``, and
+    no "Training finished" line -- the reference's trial leaves ``run_training`` with the exception there."""
+    logger.error(f"{type(exc).__name__}: {exc}")
+
+
+def diverged_trials(result):
+    """Trial numbers (1-based) whose result holds an ``AnomalyError`` instead of metrics."""
+    return [k + 1 for k, r in enumerate(result) if isinstance(r[0], AnomalyError)]
+
+
 def run_training(job_number, work_dir, train_config, verbose, data_file, timeout_hours=0,
                  logger=logging.getLogger("training"), host_rng=None, init_lock=None):
     """``host_rng`` / ``init_lock``: thread mode (several trials in this process) -- the trial's own host generator, and
-    the lock under which the global generator is seeded for the construction of ITS networks."""
+    the lock under which the global generator is seeded for the construction of ITS networks.  Returns
+    ``(metrics, time_used)``, or ``(AnomalyError, time_used)`` for a trial that diverged (later trials still run)."""
     work_dir = f"{work_dir}/training/job_{job_number + 1}"
     os.makedirs(work_dir, exist_ok=True)
     if _is_lead_rank():
@@ -74,6 +87,9 @@ def run_training(job_number, work_dir, train_config, verbose, data_file, timeout
             timer.start()
         try:
             metrics = trainer.train()
+        except AnomalyError as exc:
+            log_diverged(logger, exc)
+            return exc, time.time() - start
         finally:
             if timer is not None:
                 timer.cancel()
@@ -93,6 +109,9 @@ def run_training(job_number, work_dir, train_config, verbose, data_file, timeout
     signal.setitimer(signal.ITIMER_REAL, max(0.0, float(timeout_hours) * 3600.0))
     try:
         metrics = trainer.train()
+    except AnomalyError as exc:               # data parallel: every rank raises it at the same epoch
+        log_diverged(logger, exc)
+        return exc, time.time() - start
     finally:
         signal.setitimer(signal.ITIMER_REAL, 0.0)
         trainer.engine.release()              # graphs, workspaces and streams back now: more trials may follow
@@ -135,7 +154,7 @@ def run_trials_batched(jobs, per_batch, work_dir, train_config, verbose, data_fi
     """The trials ``jobs`` of this process, ``per_batch`` at a time, each group trained in LOCKSTEP: every training step
     of the group is one launch sequence with ``gridDim.z = trials`` (``rankaae_amd.trainer.train_trials_batched``; both
     networks).  Seeds, files and log lines per trial as in the thread mode: ``[(k, metrics, time_used)]``."""
-    from rankaae_amd.trainer import train_trials_batched
+    from rankaae_amd.trainer import TrialsDiverged, train_trials_batched
     from rankaae_amd.trial_batch import BatchingRefused
     plain_config = train_config
     if train_config.get("ae_form", None) != "FC" and train_config.get("tile_rows_mult", None) is None:
@@ -170,8 +189,12 @@ def run_trials_batched(jobs, per_batch, work_dir, train_config, verbose, data_fi
             timer.daemon = True
             timer.start()
         refused = None
+        errors = [None] * len(group)
         try:
             metrics = train_trials_batched(trainers)
+        except TrialsDiverged as exc:
+            # some trials of the group diverged (AnomalyError); the others trained to the end and wrote their files
+            metrics, errors = exc.results, exc.errors
         except BatchingRefused as exc:
             # the first step of this configuration meets a kernel without the batched form (the per-layer conv kernels
             # of `fused_blocks: false`): `trial_mode: batched` says so; `auto` trains the group in threads instead, from
@@ -198,7 +221,11 @@ def run_trials_batched(jobs, per_batch, work_dir, train_config, verbose, data_fi
             out += run_trials_threaded(group, min(4, len(group)), work_dir, plain_config, verbose, data_file, timeout, trial_seed)
             continue
         time_used = time.time() - start
-        for k, m, logger in zip(group, metrics, loggers):
+        for k, m, err, logger in zip(group, metrics, errors, loggers):
+            if err is not None:
+                log_diverged(logger, err)
+                out.append((k, err, time_used))
+                continue
             logger.info(m)
             logger.info(f"Training finished. Time used: {time_used:.2f}s.\n\n")
             out.append((k, m, time_used))
@@ -338,6 +365,12 @@ def main():
                 " ".join([f"{t:.2f}s" for t in time_trials]))
     end = time.time()
     logger.info(f"Total time used: {end - start:.2f}s for {trials} trails ({(end - start) / trials:.2f} each on average).")
+    failed = diverged_trials(result)
+    if failed:
+        # the reference's map_sync raises once its tasks are done: the other trials have written their files
+        msg = f"Trials {failed} diverged: NaN gradients (detect_anomaly); see their messages.txt."
+        logger.error(msg)
+        sys.exit(msg)
     logger.info("END\n\n")
 
 

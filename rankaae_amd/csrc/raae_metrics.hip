@@ -47,6 +47,10 @@ __device__ __forceinline__ void style_rank_body(const float* __restrict__ z, int
             eqb += e & (jj < before);
         }
     }
+    // The slot stays in [0, n) for any input, NaN included: it counts the disjoint sets {j : x_j < x_i} and
+    // {j < i : x_j == x_i}, neither of which holds j = i, and every comparison with a NaN is false (a NaN element and
+    // its neighbours may then share a slot -- a wrong W, never a store out of the column).  A diverged trial's grid
+    // plane of a TrialBatch keeps running this kernel.
     if (i < n) {
         const double pivot = (double)z[(size_t)(n / 2) * k + c];
         rank[(size_t)c * n + i] = (double)less + 0.5 * (double)(eq + 1);

@@ -12,9 +12,19 @@ namespace {
 // skipped (the reference skips params whose .grad is None, trainer.py:318-321).
 struct AdamArgs { float* p; float* m; float* v; const float* g_slabs; long slab_stride; const unsigned short* seg_nslab;
                   long n; const double* hyper; const int* step; int decoupled; };
+
+// NaN check of the checked instances (CHK = true; raae_optim_step_chk): every lane keeps whether a gradient it summed
+// was NaN, the wave votes once after its loop, and one lane of a wave that saw one writes the optimizer's step count
+// (1-based) into *nan_step if that still holds 0 -- the first step stays.  NaN only, as autograd's anomaly mode: an
+// Inf gradient turns m / v / p into NaN and the next step's gradient is NaN.  Nothing else of the update changes.
+__device__ __forceinline__ void nan_vote(bool seen, int* nan_step, const int* step) {
+    if (__ballot(seen) != 0ull && (threadIdx.x & 63) == 0) atomicCAS(nan_step, 0, step[0]);
+}
+
+template <bool CHK>
 __device__ __forceinline__ void adam_body(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
                                           const unsigned short* seg_nslab, long n, const double* hyper,
-                                          const int* step, int decoupled) {
+                                          const int* step, int decoupled, int* nan_step) {
     __shared__ float s_sc[8];
     if (threadIdx.x == 0) {
         const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
@@ -32,6 +42,7 @@ __device__ __forceinline__ void adam_body(float* p, float* m, float* v, const fl
     __syncthreads();
     const float decay = s_sc[0], w1 = s_sc[1], b2f = s_sc[2], omb2 = s_sc[3], nstep = s_sc[4], bc2s = s_sc[5],
                 epsf = s_sc[6], wdf = s_sc[7];
+    bool seen = false;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int ns = seg_nslab[i >> 6];
         if (ns == 0) continue;
@@ -46,6 +57,7 @@ __device__ __forceinline__ void adam_body(float* p, float* m, float* v, const fl
             for (int u = 0; u < 8; ++u) g += t[u];
         }
         for (; s < ns; ++s) g += g_slabs[(size_t)s * slab_stride + i];
+        if (CHK) seen |= __builtin_isnan(g);
         float pv = p[i];
         if (decoupled) pv = pv * decay; else if (wdf != 0.f) g = g + wdf * pv;
         float mv = m[i], vv = v[i];
@@ -56,20 +68,33 @@ __device__ __forceinline__ void adam_body(float* p, float* m, float* v, const fl
         pv = pv + (nstep * mv) / denom;
         p[i] = pv; m[i] = mv; v[i] = vv;
     }
+    if (CHK) nan_vote(seen, nan_step, step);
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
-    adam_body(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled);
+    adam_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr);
 }
 __global__ __launch_bounds__(256) void adam_kernel_m(const AdamArgs* t) {
     const AdamArgs a = t[blockIdx.z];
-    adam_body(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled);
+    adam_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr);
+}
+// checked twins: the argument block of the unchecked kernel + the flag word
+struct AdamChkArgs { AdamArgs a; int* nan_step; };
+__global__ __launch_bounds__(256) void adam_chk_kernel(AdamChkArgs c) {
+    const AdamArgs& a = c.a;
+    adam_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, c.nan_step);
+}
+__global__ __launch_bounds__(256) void adam_chk_kernel_m(const AdamChkArgs* t) {
+    const AdamChkArgs c = t[blockIdx.z];
+    const AdamArgs& a = c.a;
+    adam_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, c.nan_step);
 }
 
 // Same update with the slabs of an element spread over 8 lanes: for ranges whose tensors have many slabs.
+template <bool CHK>
 __device__ __forceinline__ void adam_wide_body(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
                                                const unsigned short* seg_nslab, long n, const double* hyper,
-                                               const int* step, int decoupled) {
+                                               const int* step, int decoupled, int* nan_step) {
     __shared__ float s_sc[8];
     if (threadIdx.x == 0) {
         const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
@@ -92,6 +117,7 @@ __device__ __forceinline__ void adam_wide_body(float* p, float* m, float* v, con
     // thread per element the 256 slabs of a conv weight were 32 dependent round trips (28 us per step phase).
     const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;
     const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+    bool seen = false;
     for (long base = wave0; base < n; base += (long)gridDim.x * 32) {
         const long i = base + el;                       // n is a multiple of 64: i < n whenever base < n
         const int ns = seg_nslab[i >> 6];
@@ -111,6 +137,7 @@ __device__ __forceinline__ void adam_wide_body(float* p, float* m, float* v, con
         g += __shfl_xor(g, 16, 64);
         g += __shfl_xor(g, 32, 64);
         if (ch != 0) continue;
+        if (CHK) seen |= __builtin_isnan(g);
         float pv = p[i];
         if (decoupled) pv = pv * decay; else if (wdf != 0.f) g = g + wdf * pv;
         float mv = m[i], vv = v[i];
@@ -121,14 +148,26 @@ __device__ __forceinline__ void adam_wide_body(float* p, float* m, float* v, con
         pv = pv + (nstep * mv) / denom;
         p[i] = pv; m[i] = mv; v[i] = vv;
     }
+    if (CHK) nan_vote(seen, nan_step, step);
 }
 
 __global__ __launch_bounds__(256) void adam_wide_kernel(AdamArgs a) {
-    adam_wide_body(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled);
+    adam_wide_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr);
 }
 __global__ __launch_bounds__(256) void adam_wide_kernel_m(const AdamArgs* t) {
     const AdamArgs a = t[blockIdx.z];
-    adam_wide_body(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled);
+    adam_wide_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr);
+}
+__global__ __launch_bounds__(256) void adam_wide_chk_kernel(AdamChkArgs c) {
+    const AdamArgs& a = c.a;
+    adam_wide_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
+                         c.nan_step);
+}
+__global__ __launch_bounds__(256) void adam_wide_chk_kernel_m(const AdamChkArgs* t) {
+    const AdamChkArgs c = t[blockIdx.z];
+    const AdamArgs& a = c.a;
+    adam_wide_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
+                         c.nan_step);
 }
 
 // ---- RAdam and AdaBound (torch_optimizer 0.1.0, the optimizer_name values the reference takes from that package) ----
@@ -222,10 +261,11 @@ __device__ __forceinline__ void optim_scalars(const OptimArgs& a, float (&sc)[OP
     for (int k = 0; k < OPT_NSC; ++k) sc[k] = s_sc[k];
 }
 
-template <int RULE>
-__device__ __forceinline__ void optim_body(const OptimArgs& a) {
+template <int RULE, bool CHK>
+__device__ __forceinline__ void optim_body(const OptimArgs& a, int* nan_step) {
     float sc[OPT_NSC];
     optim_scalars<RULE>(a, sc);
+    bool seen = false;
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
         const int ns = a.seg_nslab[i >> 6];
         if (ns == 0) continue;
@@ -239,18 +279,21 @@ __device__ __forceinline__ void optim_body(const OptimArgs& a) {
             for (int u = 0; u < 8; ++u) g += t[u];
         }
         for (; s < ns; ++s) g += a.g_slabs[(size_t)s * a.slab_stride + i];
+        if (CHK) seen |= __builtin_isnan(g);
         float pv = a.p[i], mv = a.m[i], vv = a.v[i];
         OptRule<RULE>::update(sc, pv, mv, vv, g);
         a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
     }
+    if (CHK) nan_vote(seen, nan_step, a.step);
 }
 
-template <int RULE>
-__device__ __forceinline__ void optim_wide_body(const OptimArgs& a) {
+template <int RULE, bool CHK>
+__device__ __forceinline__ void optim_wide_body(const OptimArgs& a, int* nan_step) {
     float sc[OPT_NSC];
     optim_scalars<RULE>(a, sc);
     const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;   // adam_wide_body's lane split and shuffle tree
     const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+    bool seen = false;
     for (long base = wave0; base < a.n; base += (long)gridDim.x * 32) {
         const long i = base + el;                       // n is a multiple of 64: i < n whenever base < n
         const int ns = a.seg_nslab[i >> 6];
@@ -270,21 +313,46 @@ __device__ __forceinline__ void optim_wide_body(const OptimArgs& a) {
         g += __shfl_xor(g, 16, 64);
         g += __shfl_xor(g, 32, 64);
         if (ch != 0) continue;
+        if (CHK) seen |= __builtin_isnan(g);
         float pv = a.p[i], mv = a.m[i], vv = a.v[i];
         OptRule<RULE>::update(sc, pv, mv, vv, g);
         a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
     }
+    if (CHK) nan_vote(seen, nan_step, a.step);
 }
 
-template <int RULE> __global__ __launch_bounds__(256) void optim_kernel(OptimArgs a) { optim_body<RULE>(a); }
+template <int RULE> __global__ __launch_bounds__(256) void optim_kernel(OptimArgs a) { optim_body<RULE, false>(a, nullptr); }
 template <int RULE> __global__ __launch_bounds__(256) void optim_kernel_m(const OptimArgs* t) {
     const OptimArgs a = t[blockIdx.z];
-    optim_body<RULE>(a);
+    optim_body<RULE, false>(a, nullptr);
 }
-template <int RULE> __global__ __launch_bounds__(256) void optim_wide_kernel(OptimArgs a) { optim_wide_body<RULE>(a); }
+template <int RULE> __global__ __launch_bounds__(256) void optim_wide_kernel(OptimArgs a) { optim_wide_body<RULE, false>(a, nullptr); }
 template <int RULE> __global__ __launch_bounds__(256) void optim_wide_kernel_m(const OptimArgs* t) {
     const OptimArgs a = t[blockIdx.z];
-    optim_wide_body<RULE>(a);
+    optim_wide_body<RULE, false>(a, nullptr);
+}
+// checked twins (raae_optim_step_chk)
+struct OptimChkArgs { OptimArgs a; int* nan_step; };
+template <int RULE> __global__ __launch_bounds__(256) void optim_chk_kernel(OptimChkArgs c) {
+    optim_body<RULE, true>(c.a, c.nan_step);
+}
+template <int RULE> __global__ __launch_bounds__(256) void optim_chk_kernel_m(const OptimChkArgs* t) {
+    const OptimChkArgs c = t[blockIdx.z];
+    optim_body<RULE, true>(c.a, c.nan_step);
+}
+template <int RULE> __global__ __launch_bounds__(256) void optim_wide_chk_kernel(OptimChkArgs c) {
+    optim_wide_body<RULE, true>(c.a, c.nan_step);
+}
+template <int RULE> __global__ __launch_bounds__(256) void optim_wide_chk_kernel_m(const OptimChkArgs* t) {
+    const OptimChkArgs c = t[blockIdx.z];
+    optim_wide_body<RULE, true>(c.a, c.nan_step);
+}
+
+// the grid of every update kernel: above 16 slabs 32 elements per workgroup (8 lanes per element), else one per thread
+inline dim3 optim_grid(long n, int max_nslab) {
+    long g = max_nslab > 16 ? (n + 31) / 32 : (n + 255) / 256;
+    if (g > 4096) g = 4096;
+    return dim3((int)g);
 }
 
 template <int RULE>
@@ -298,6 +366,15 @@ void launch_optim(const OptimArgs& a, int max_nslab, hipStream_t stream) {
         if (g > 4096) g = 4096;
         raae::launch(optim_kernel<RULE>, optim_kernel_m<RULE>, dim3((int)g), dim3(256), 0, stream, a);
     }
+}
+
+template <int RULE>
+void launch_optim_chk(const OptimChkArgs& c, int max_nslab, hipStream_t stream) {
+    if (max_nslab > 16)
+        raae::launch(optim_wide_chk_kernel<RULE>, optim_wide_chk_kernel_m<RULE>, optim_grid(c.a.n, max_nslab), dim3(256), 0,
+                     stream, c);
+    else
+        raae::launch(optim_chk_kernel<RULE>, optim_chk_kernel_m<RULE>, optim_grid(c.a.n, max_nslab), dim3(256), 0, stream, c);
 }
 
 __global__ void tick_kernel(int* steps, int n, unsigned mask, unsigned long long* rng_counter, int* cursor,
@@ -537,6 +614,24 @@ extern "C" int raae_optim_step(float* p, float* m, float* v, const float* g_slab
     const OptimArgs a = {p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step};
     if (rule == RAAE_OPT_RADAM) launch_optim<RAAE_OPT_RADAM>(a, max_nslab, (hipStream_t)stream);
     else launch_optim<RAAE_OPT_ADABOUND>(a, max_nslab, (hipStream_t)stream);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_optim_step_chk(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                                   const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
+                                   int max_nslab, int* nan_step, void* stream) {
+    RAAE_CHECK_ARG(rule >= RAAE_OPT_ADAM && rule <= RAAE_OPT_ADABOUND && nan_step);
+    RAAE_CHECK_ARG(p && m && v && g_slabs && seg_nslab && hyper && step && n > 0 && (n % 64) == 0 && max_nslab >= 0);
+    const hipStream_t st = (hipStream_t)stream;
+    if (rule == RAAE_OPT_ADAM || rule == RAAE_OPT_ADAMW) {
+        const AdamChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, rule == RAAE_OPT_ADAMW}, nan_step};
+        if (max_nslab > 16) raae::launch(adam_wide_chk_kernel, adam_wide_chk_kernel_m, optim_grid(n, max_nslab), dim3(256), 0, st, c);
+        else raae::launch(adam_chk_kernel, adam_chk_kernel_m, optim_grid(n, max_nslab), dim3(256), 0, st, c);
+    } else {
+        const OptimChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step}, nan_step};
+        if (rule == RAAE_OPT_RADAM) launch_optim_chk<RAAE_OPT_RADAM>(c, max_nslab, st);
+        else launch_optim_chk<RAAE_OPT_ADABOUND>(c, max_nslab, st);
+    }
     RAAE_LAUNCH_RET();
 }
 

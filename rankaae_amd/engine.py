@@ -25,7 +25,7 @@ from torch import nn
 
 from . import _lib, ops
 from .metrics import StyleMetrics
-from .parameter import check_optimizer
+from .parameter import check_optimizer, detect_anomaly_on
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -603,7 +603,16 @@ class StepEngine:
         self._tail_ev = [torch.cuda.Event(), torch.cuda.Event()] if self.defer_tail else None
         self.tail_state = [torch.zeros(3, dtype=torch.int64, device=device) for _ in range(2)] if self.defer_tail else None
         self.alpha_dev = torch.zeros(1, device=device)
-        self.loss_out = torch.zeros(8, device=device)
+        # what losses() reads back at the end of an epoch, in ONE copy: the 8 loss slots (fp32) and, build-only key
+        # `detect_anomaly` (default on: the reference's torch.autograd.set_detect_anomaly(True)), one int flag word per
+        # optimizer in OPT_NAMES order -- 0, or the step count of the first step whose gradient held a NaN (written by
+        # the checked update kernels, raae_optim_step_chk).  Written inside the captured step graphs like every buffer
+        # of the step; kept by release() like loss_out, so that anomaly() still answers afterwards.
+        self.detect_anomaly = detect_anomaly_on(self.cfg)
+        self._epoch_words = torch.zeros(16, dtype=torch.int32, device=device)
+        self.loss_out = self._epoch_words[:8].view(torch.float32)
+        self.nan_flags = self._epoch_words[8:8 + len(OPT_NAMES)]
+        self._nan_host = None                 # the flags as losses() read them; None once a step has been launched since
         self.taps = gaussian_taps(17, 3.0).tolist()
         self.bn_counts = {}
         self.plans = {}
@@ -908,7 +917,10 @@ class StepEngine:
             g, seg, max_slab = self.G_flat[lo:], self.seg_ones[lo // 64:], 1
         else:
             g, seg, max_slab = self.G[0, lo:], P.seg[name][lo // 64:], P.max_slab[name]
-        if o.rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW):
+        if self.detect_anomaly:     # the same update by the checked twins of its kernels (all four rules)
+            ops.optim_step(self.arena.P[lo:], o.m, o.v, g, self.arena.n, seg, n, o.rule, o.hyper,
+                           self.steps_dev[o.index:], max_slab, nan_step=self.nan_flags[o.index:o.index + 1])
+        elif o.rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW):
             ops.adam_step(self.arena.P[lo:], o.m, o.v, g, self.arena.n, seg, n, o.hyper, self.steps_dev[o.index:],
                           self.decoupled, max_slab)
         else:           # RAdam / AdaBound: raae_optim_step, same arena, slabs and step count
@@ -1160,6 +1172,7 @@ class StepEngine:
             raise ValueError("Expected more than 1 value per channel when training, got input size "
                              f"torch.Size([{b}, {self.nstyle}])")
         P = self.plan(b)
+        self._nan_host = None
         stride = self.cursor_stride if self.cursor_stride is not None else b
         if self._host_cursor + b > len(self.train_spec):
             raise RuntimeError(f"epoch exhausted: rows [{self._host_cursor}, {self._host_cursor + b}) exceed the "
@@ -1288,7 +1301,7 @@ class StepEngine:
         saved_graph = self.use_graph
         self.use_graph = False
         torch.cuda.synchronize()
-        bufs = [self.arena.P, self.steps_dev, self.loss_out, self.rng_counter, self.cursor] + \
+        bufs = [self.arena.P, self.steps_dev, self._epoch_words, self.rng_counter, self.cursor] + \
                [t for o in self.opts.values() for t in (o.m, o.v)] + \
                [b_ for mod in (self.enc_mod, self.dec_mod, self.dis_mod) for b_ in mod.buffers()]
         snap = [t.clone() for t in bufs]
@@ -1410,8 +1423,25 @@ class StepEngine:
 
     @_on_stream
     def losses(self):
-        v = self.loss_out.cpu().tolist()
+        words = self._epoch_words.cpu()       # the loss slots and the NaN flag words: one readback
+        self._nan_host = words[8:8 + len(OPT_NAMES)].tolist()
+        v = words[:8].view(torch.float32).tolist()
         return {k: v[i] for k, i in LOSS_SLOTS.items()}
+
+    @_on_stream
+    def anomaly(self):
+        """``None``, or ``(phase, step)``: the optimizer phase (``OPT_NAMES``) and its 1-based step count of the first
+        update whose gradient held a NaN (``detect_anomaly``) -- the earliest step, the first phase of the step on a
+        tie.  Uses the flags the last ``losses()`` read when no step has been launched since (no extra
+        synchronisation at the epoch boundary); otherwise reads them now."""
+        flags = self._nan_host
+        if flags is None:
+            flags = self.nan_flags.tolist()
+        hits = [(step, i) for i, step in enumerate(flags) if step != 0]
+        if not hits:
+            return None
+        step, i = min(hits)
+        return OPT_NAMES[i], step
 
     # -- validation (trainer.py:206-268): eval-mode forward of the whole validation set
     @_on_stream

@@ -305,20 +305,30 @@ def adam_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, decouple
 OPT_RULE_NAMES = {_lib.OPT_ADAM: "Adam", _lib.OPT_ADAMW: "AdamW", _lib.OPT_RADAM: "RAdam", _lib.OPT_ADABOUND: "AdaBound"}
 
 
-def optim_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab=512):
+def optim_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab=512, nan_step=None):
     """``raae_optim_step``: one step of update rule ``rule`` (``_lib.OPT_*``); ``hyper`` is the device block
-    {lr, beta1, beta2, eps, weight_decay, base_lr, final_lr, gamma} (the Adam rules read the first five)."""
+    {lr, beta1, beta2, eps, weight_decay, base_lr, final_lr, gamma} (the Adam rules read the first five).
+    ``nan_step`` (a device int32 word): the same update with the NaN check of ``raae_optim_step_chk`` -- the word
+    receives the step count of the first step whose gradient held a NaN, and stays 0 until then."""
     if rule not in OPT_RULE_NAMES:
         raise ValueError(f"unknown optimizer rule {rule!r}")
     if hyper.numel() < (5 if rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW) else 8):       # what the kernel reads
         raise ValueError(f"{OPT_RULE_NAMES[rule]}: hyper holds {hyper.numel()} values, the rule reads 8")
+    family = "adam_kernel" if rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW) else "optim_kernel"
+    if nan_step is not None:
+        def launch_chk():
+            check(_lib.load().raae_optim_step_chk(_ptr(p), _ptr(m), _ptr(v), _ptr(g_slabs), slab_stride,
+                                                  _ptr(seg_nslab, torch.int16), n, int(rule), _ptr(hyper, torch.float64),
+                                                  _ptr(step, torch.int32), int(max_nslab), _ptr(nan_step, torch.int32),
+                                                  _stream()), "raae_optim_step_chk")
+        _probed(family, 28 * n, launch_chk, tag=OPT_RULE_NAMES[rule])
+        return
 
     def launch():
         check(_lib.load().raae_optim_step(_ptr(p), _ptr(m), _ptr(v), _ptr(g_slabs), slab_stride,
                                           _ptr(seg_nslab, torch.int16), n, int(rule), _ptr(hyper, torch.float64),
                                           _ptr(step, torch.int32), int(max_nslab), _stream()),
               "raae_optim_step")
-    family = "adam_kernel" if rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW) else "optim_kernel"
     _probed(family, 28 * n, launch, tag=OPT_RULE_NAMES[rule])
 
 

@@ -28,6 +28,17 @@ def check_optimizer(cfg):
                     raise ValueError(f"{name}: invalid learning rate {lr!r} ({key} * lr_base); {name} needs lr > 0")
 
 
+def detect_anomaly_on(cfg):
+    """Build-only key ``detect_anomaly`` (default ``true``: the reference turns on
+    ``torch.autograd.set_detect_anomaly(True)`` at import, sc/clustering/trainer.py:11).  On, the optimizer updates
+    check every parameter gradient for NaN on the device and ``Trainer.train`` raises ``AnomalyError`` at the end of
+    the epoch in which one appeared; ``false`` launches the unchecked updates."""
+    value = cfg.get("detect_anomaly", True)
+    if not isinstance(value, bool):
+        raise ValueError(f"detect_anomaly must be true or false, not {value!r}")
+    return value
+
+
 class Parameters:
     def __init__(self, parameter_dict):
         object.__setattr__(self, "_parameter_dict", parameter_dict)

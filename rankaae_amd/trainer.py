@@ -11,6 +11,8 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
   ``use_graph`` True: replay one captured hipGraph per step
   ``seed``      Philox seed (``rng_mode: philox``); default: drawn from the global torch generator, i.e. a different
                 random stream for every trial of a run, as in the reference (whose trials are independent draws)
+  ``detect_anomaly`` True (default, the reference's ``set_detect_anomaly(True)``): a NaN parameter gradient ends
+                ``train()`` with ``AnomalyError`` at the end of its epoch, before anything of that epoch is logged or saved
 
 Data parallel (the north star's replacement of the ipyparallel trial farm): started under
 ``torch.distributed.run`` (WORLD_SIZE > 1) every rank builds the same ``Trainer``; rank r steps rows
@@ -31,7 +33,34 @@ import torch
 from .dataloader import get_dataloaders
 from .engine import StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
-from .parameter import Parameters, check_optimizer
+from .parameter import Parameters, check_optimizer, detect_anomaly_on
+
+
+class AnomalyError(RuntimeError):
+    """A parameter gradient held a NaN (config key ``detect_anomaly``): the reference's anomaly mode raises
+    ``RuntimeError: Function '...Backward0' returned nan values in its ...th output.`` from the backward of that step.
+    Here the optimizer update of ``phase`` (``engine.OPT_NAMES``) saw it at its step count ``step`` (1-based), and
+    ``Trainer.train`` raises at the end of ``epoch``, before that epoch's log row, checkpoints and schedulers."""
+
+    def __init__(self, phase, step, epoch):
+        self.phase, self.step, self.epoch = phase, step, epoch
+        what = f"{phase} backward" if phase is not None else "backward on another rank"
+        super().__init__(f"Function '{what}' returned nan values in its parameter gradient at optimizer step {step}, "
+                         f"epoch {epoch} (detect_anomaly)")
+
+    def __reduce__(self):           # pickles through train_sc's worker processes
+        return type(self), (self.phase, self.step, self.epoch)
+
+
+class TrialsDiverged(RuntimeError):
+    """``train_trials_batched``: some trials of the batch raised ``AnomalyError``; the others trained to the end and
+    wrote their files.  ``results[i]``: trial i's metrics (None where it diverged); ``errors[i]``: its
+    ``AnomalyError`` (None where it finished)."""
+
+    def __init__(self, results, errors):
+        self.results, self.errors = results, errors
+        bad = [i for i, e in enumerate(errors) if e is not None]
+        super().__init__(f"trials {bad} of the batch diverged: " + "; ".join(str(errors[i]) for i in bad))
 
 
 def alpha(epoch_percentage, step=800, limit=0.7):
@@ -84,6 +113,7 @@ class Trainer:
                              "(SURVEY.md finding 4)")
         cfg = config_parameters.to_dict()
         check_optimizer(cfg)        # before anything touches the GPU
+        self.detect_anomaly = detect_anomaly_on(cfg)
         self.world, self.rank, self.pg = self._data_parallel_setup(device)
         # one draw from the global generator per trial (also when `seed` is given, so that the generator's state
         # does not depend on the key): trials of one run then use different noise / dropout / latent streams
@@ -196,6 +226,7 @@ class Trainer:
         vds = self.val_loader.dataset
         val_spec = torch.as_tensor(vds.spec, dtype=torch.float32).contiguous().to(self.device)
         val_aux = torch.as_tensor(vds.aux, dtype=torch.float32).contiguous().to(self.device)
+        self._val_split = (val_spec, val_aux)       # (train_trials_batched: a diverged trial's plane still validates)
         n_train, bs = len(self.train_loader.dataset), self.train_loader.batch_size
         # single GPU: every batch of the reference's loader incl. the ragged last one; data parallel: every full
         # global batch of world * bs rows, the tail split evenly over the ranks (parallel.epoch_schedule)
@@ -221,6 +252,14 @@ class Trainer:
                 gc.freeze()
                 self._gc_frozen = True
             tl = eng.losses()
+            if self.detect_anomaly:
+                nan = eng.anomaly()     # read by losses(): no synchronisation of its own
+                # data parallel: the gradients were all-reduced before the update, so every rank saw the NaN; the
+                # agreement still makes all ranks raise here together (none is left waiting in a collective)
+                if self.world > 1 and any_rank(nan is not None, self.device, self.pg) and nan is None:
+                    nan = (None, 0)
+                if nan is not None:
+                    raise AnomalyError(nan[0], nan[1], epoch)
             if not smooth:
                 tl["smooth"] = 0.0
             if self.world > 1:
@@ -301,36 +340,53 @@ def train_trials_batched(trainers, callbacks=None):
     sequence with ``gridDim.z = T`` (``rankaae_amd.trial_batch.TrialBatch``; dense networks).  Everything around the
     step -- epoch permutation, validation, metrics, schedulers, checkpoints, log rows -- is each trainer's own code,
     run trial after trial between the steps.  Returns the trials' metrics lists.  A trial that asks to stop
-    (``request_stop``) ends the whole batch with the reference's exception: the trials advance together."""
+    (``request_stop``) ends the whole batch with the reference's exception: the trials advance together.  A trial whose
+    ``train()`` raises ``AnomalyError`` (``detect_anomaly``) ends alone: the others go on, and once they have finished
+    (and written their files) ``TrialsDiverged`` carries every trial's metrics or error."""
     from .trial_batch import TrialBatch
     callbacks = callbacks or [None] * len(trainers)
     batch = TrialBatch([t.engine for t in trainers])
     gens = [t._train_epochs(cb) for t, cb in zip(trainers, callbacks)]
-    results = [None] * len(trainers)
+    T = len(trainers)
+    results, errors = [None] * T, [None] * T
+
+    def advance(i, answer):
+        try:
+            return next(gens[i]) if answer is None else gens[i].send(answer)
+        except StopIteration as done:
+            results[i] = done.value
+        except AnomalyError as exc:
+            errors[i] = exc
+        return None
+
     try:
-        reqs = []
-        for i, g in enumerate(gens):
-            try:
-                reqs.append(next(g))
-            except StopIteration as done:
-                results[i] = done.value
-                reqs.append(None)
-        while not all(r is None for r in reqs):
-            if any(r is None for r in reqs) or any(r[0] != reqs[0][0] or (r[0] == "step" and r != reqs[0]) for r in reqs):
+        reqs = [advance(i, None) for i in range(T)]
+        while True:
+            live = [i for i in range(T) if reqs[i] is not None]
+            if not live:
+                break
+            r0 = reqs[live[0]]
+            finished = [i for i in range(T) if reqs[i] is None and errors[i] is None]
+            if finished or any(reqs[i][0] != r0[0] or (r0[0] == "step" and reqs[i] != r0) for i in live):
                 raise RuntimeError(f"the trials of a batch left lockstep: {[r and r[:1] for r in reqs]}")
-            if reqs[0][0] == "step":
-                batch.step(reqs[0][1], smooth=reqs[0][2])
-                answers = [None] * len(gens)
+            if r0[0] == "step":
+                # a diverged trial's grid plane is stepped too (the batch's launch sequence covers all T planes, and
+                # planes are independent); its results are never read.  Nobody starts its epochs any more: it reads
+                # the first rows of its last permutation at every step
+                for i in range(T):
+                    if errors[i] is not None:
+                        trainers[i].engine.seek(0)
+                batch.step(r0[1], smooth=r0[2])
+                answers = [None] * T
             else:
-                answers = batch.validate([r[1] for r in reqs], [r[2] for r in reqs])
-            nxt = []
-            for i, g in enumerate(gens):
-                try:
-                    nxt.append(next(g) if answers[i] is None else g.send(answers[i]))
-                except StopIteration as done:
-                    results[i] = done.value
-                    nxt.append(None)
-            reqs = nxt
+                # ... and validated on its own split, its answer dropped.  Its NaN weights keep every kernel of the
+                # validation in bounds: the one index formed from the data, the sorted slot of style_rank_kernel
+                # (raae_metrics.hip), counts comparisons that are false for NaN and stays in [0, n)
+                val = [reqs[i][1:] if reqs[i] is not None else trainers[i]._val_split for i in range(T)]
+                answers = batch.validate([v[0] for v in val], [v[1] for v in val])
+            reqs = [advance(i, answers[i]) if reqs[i] is not None else None for i in range(T)]
+        if any(e is not None for e in errors):
+            raise TrialsDiverged(results, errors)
         return results
     finally:
         for g in gens:
