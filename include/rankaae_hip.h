@@ -460,6 +460,33 @@ int raae_block_wgrad(const raae_block_wgrad_t* a, int* nslab, void* stream);
 int raae_block_bwd_b_wgrad(const raae_block_bwd_b_t* b, const raae_block_wgrad_t* w, int* nparts, int* nslab,
                            void* stream);
 
+/* TWO launches of the fused conv-network kernels that do not depend on each other, as ONE launch: the leading
+ * workgroups run body x, the rest body y, each exactly as in its own launch (ABI 20).  Where a training phase ends in
+ * a backward pass of one network and the next phase begins with a forward pass of the other (trainer.py:175-200: the
+ * mutual-information phase ends in the decoder's backward, the smoothness phase starts with the encoder's forward),
+ * the forward's launches ride in the backward's -- after the update of the network they read, which is why the
+ * Adam / AdamW update of a slice of an optimizer's range is a body too.  kind_* and what args_* points at:
+ *   RAAE_CO_FWD_A  raae_block_fwd_a_t        RAAE_CO_FWD_B  raae_block_fwd_b_t        RAAE_CO_BWD_A  raae_block_bwd_a_t
+ *   RAAE_CO_BWD_B_WGRAD  raae_co_bwd_b_wgrad_t (raae_block_bwd_b_wgrad's arguments)
+ *   RAAE_CO_ADAM         raae_co_adam_t (raae_adam_step's arguments; nan_step != NULL: raae_optim_step_chk's)
+ * *nparts_*: what the body's own entry point returns in *nparts (nothing for RAAE_CO_ADAM).  One launch for the
+ * pairs of the 256-point networks' block shapes below 1024 rows (backward of decoder block i with the update or with
+ * the forward of encoder block 6 - i ... ); any other pair runs as the two launches of the bodies' own entry points, x first. */
+#define RAAE_CO_FWD_A 0
+#define RAAE_CO_FWD_B 1
+#define RAAE_CO_BWD_A 2
+#define RAAE_CO_BWD_B_WGRAD 3
+#define RAAE_CO_ADAM 4
+typedef struct { const raae_block_bwd_b_t* b; const raae_block_wgrad_t* w; int* nslab; } raae_co_bwd_b_wgrad_t;
+typedef struct {
+    float *p, *m, *v; const float* g_slabs; long slab_stride; const unsigned short* seg_nslab; long n;
+    int rule;                  /* RAAE_OPT_ADAM | RAAE_OPT_ADAMW */
+    const double* hyper; const int* step; int max_nslab;
+    int* nan_step;             /* NULL: unchecked */
+} raae_co_adam_t;
+int raae_co_launch(int kind_x, const void* args_x, int kind_y, const void* args_y, int* nparts_x, int* nparts_y,
+                   void* stream);
+
 /* Data parallel (replaces the reference's ipyparallel trial farm, sc/cmd/train_sc.py:25-45, per the
  * north star): out[i] = fixed-order sum of the slabs of element i -- the flat gradient that is then
  * averaged across ranks with one RCCL all-reduce per phase and fed to raae_adam_step as a single slab. */
@@ -555,7 +582,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 19
+#define RAAE_ABI_VERSION 20
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -1099,7 +1099,7 @@ __global__ __launch_bounds__(256) void block_bwd_b_kernel_m(const BlockBwdBArgs*
 typedef raae_block_bwd_a_t BlockBwdAArgs;
 
 template <int KIND, bool BIG>        // see block_fwd_a_kernel
-__device__ __forceinline__ void block_bwd_a_body(const BlockBwdAArgs& a, float* dyn) {
+__device__ __forceinline__ void block_bwd_a_body(const BlockBwdAArgs& a, const int bx, const int gx, float* dyn) {
 #define SH(f) (KIND >= 0 ? kBlk[KIND < 0 ? 0 : KIND].f : a.f)
     constexpr bool kHalo1 = KIND >= 0 && !kBlk[KIND < 0 ? 0 : KIND].cv1.transposed && kBlk[KIND < 0 ? 0 : KIND].cv1.pad_replicate &&
                             kBlk[KIND < 0 ? 0 : KIND].Lin % 8 == 0 && kBlk[KIND < 0 ? 0 : KIND].cv1.pad <= 7 &&
@@ -1154,7 +1154,7 @@ __device__ __forceinline__ void block_bwd_a_body(const BlockBwdAArgs& a, float* 
                       aligned16(a.g1.raw) && aligned16(a.g1.u) && aligned16(a.dT1) && aligned16(a.dSh) &&
                       aligned16(a.dE2) && (!SH(has_excit) || (aligned16(a.ge.g) && aligned16(a.ge.raw) && aligned16(a.ge.u)));
     STAMP(3, 2);
-    for (int grp = blockIdx.x; grp < a.ngroups; grp += gridDim.x) {
+    for (int grp = bx; grp < a.ngroups; grp += gx) {
         const int b0 = grp * a.S, nb = min(a.S, a.B - b0);
         __syncthreads();
         STAMP(3, 3);
@@ -1468,7 +1468,7 @@ __device__ __forceinline__ void block_bwd_a_body(const BlockBwdAArgs& a, float* 
         }
     }
     STAMP(3, 7);
-    const size_t slab = (size_t)blockIdx.x * (size_t)a.slab_stride;
+    const size_t slab = (size_t)bx * (size_t)a.slab_stride;
     STAMP(3, 8);
     chan_reduce(d1, 0.0, SH(Cout), mo, res, scr, scr2);
     __syncthreads();
@@ -1482,7 +1482,7 @@ __device__ __forceinline__ void block_bwd_a_body(const BlockBwdAArgs& a, float* 
     if ((int)threadIdx.x < SH(Cin)) {
         const double* r = res4 + threadIdx.x * 4;
         if (a.dR != nullptr && a.pdR) {
-            double* pp = a.pdR + ((size_t)blockIdx.x * SH(Cin) + threadIdx.x) * 2;
+            double* pp = a.pdR + ((size_t)bx * SH(Cin) + threadIdx.x) * 2;
             pp[0] = r[0]; pp[1] = r[1];
         }
         if (SH(has_excit)) a.dslope_e2[slab + threadIdx.x] = (float)r[2];
@@ -1496,12 +1496,12 @@ __global__ __launch_bounds__(256) void block_bwd_a_kernel(BlockBwdAArgs ka) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ BlockBwdAArgs sa;
     const BlockBwdAArgs& a = raae::args_to_lds(&sa);
-    block_bwd_a_body<KIND, BIG>(a, dyn);
+    block_bwd_a_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }
 template <int KIND, bool BIG = false>
 __global__ __launch_bounds__(256) void block_bwd_a_kernel_m(const BlockBwdAArgs* table) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     __shared__ BlockBwdAArgs sa;
     const BlockBwdAArgs& a = raae::args_from_table(&sa, table);
-    block_bwd_a_body<KIND, BIG>(a, dyn);
+    block_bwd_a_body<KIND, BIG>(a, blockIdx.x, gridDim.x, dyn);
 }

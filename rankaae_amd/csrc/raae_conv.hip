@@ -1036,7 +1036,8 @@ extern "C" int raae_block_bwd_b(const raae_block_bwd_b_t* in, int* nparts, void*
     RAAE_LAUNCH_RET();
 }
 
-extern "C" int raae_block_bwd_a(const raae_block_bwd_a_t* in, int* nparts, void* stream) {
+// checks + launch geometry of backward phase A (shared by raae_block_bwd_a and raae_co_launch)
+static int prep_block_bwd_a(const raae_block_bwd_a_t* in, raae_block_bwd_a_t& a, int& grid, size_t& lds, int& kind) {
     RAAE_CHECK_ARG(in && in->B > 0 && in->Cin >= 1 && in->Cin <= CT_MAXCH && in->Cout >= 1 && in->Cout <= CT_MAXCH);
     RAAE_CHECK_ARG(grad_ok(&in->g1, in->Cout) && in->g1.has_bn && in->g1.raw && in->g1.slope);
     RAAE_CHECK_ARG(!in->has_excit || (grad_ok(&in->ge, in->Cin) && in->ge.raw && in->ge.slope && in->dslope_e2));
@@ -1044,8 +1045,8 @@ extern "C" int raae_block_bwd_a(const raae_block_bwd_a_t* in, int* nparts, void*
     RAAE_CHECK_ARG(in->has_short || (in->Cin == in->Cout && in->Lin == in->Lout));
     RAAE_CHECK_ARG(in->E1 && in->dSh && in->dT1 && in->dE2 && in->dE1 && in->dslope1 && in->dslope_e1 && in->se1);
     RAAE_CHECK_ARG(!in->pdR || (in->dR && in->in.has_bn));
-    raae_block_bwd_a_t a = *in;
-    const int kind = blk_kind_a(a.Cin, a.Cout, a.Lin, a.L1, a.Lout, a.E, a.cv1, a.has_short, a.cvs, a.has_excit, true);
+    a = *in;
+    kind = blk_kind_a(a.Cin, a.Cout, a.Lin, a.L1, a.Lout, a.E, a.cv1, a.has_short, a.cvs, a.has_excit, true);
     // strip instances (block_bwd_a_kernel: kStripA) keep an 8-float zero margin on both sides of every dT1 row
     const int gm = (kind >= 0 && strip_conv_ok(kBlk[kind].cv1) && !kBlk[kind].has_short) ? kStripMargin : 0;
     const long wfl = conv_nw(&a.cv1) + (a.has_short ? conv_nw(&a.cvs) : 0) + (long)a.E * a.Lin + (long)a.Lout * a.E;
@@ -1058,9 +1059,18 @@ extern "C" int raae_block_bwd_a(const raae_block_bwd_a_t* in, int* nparts, void*
     a.S = pick_S(per, widest, a.B, kTileBudget, 256);
     a.ngroups = (a.B + a.S - 1) / a.S;
     a.sh_lin = lg2(a.Lin); a.sh_l1 = lg2(a.L1); a.sh_lout = lg2(a.Lout); a.sh_e = lg2(a.E);
-    const int grid = a.ngroups < 512 ? a.ngroups : 512;
+    grid = a.ngroups < 512 ? a.ngroups : 512;
+    lds = sizeof(float) * ((size_t)a.S * per + wfl);
+    return 0;
+}
+
+extern "C" int raae_block_bwd_a(const raae_block_bwd_a_t* in, int* nparts, void* stream) {
+    raae_block_bwd_a_t a;
+    int grid, kind;
+    size_t lds;
+    const int rc = prep_block_bwd_a(in, a, grid, lds, kind);
+    if (rc) return rc;
     if (nparts) *nparts = grid;
-    const size_t lds = sizeof(float) * ((size_t)a.S * per + wfl);
     const bool big = use_big(a.B, kind, kFamBwdA);
     RAAE_LAUNCH_KIND_BIG(block_bwd_a_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a)
     RAAE_LAUNCH_RET();
@@ -1189,6 +1199,20 @@ __global__ __launch_bounds__(256) void block_bwd_b_wgrad_kernel_m(const BwdBWgra
     }
 }
 
+static int launch_bwd_b_wgrad(const BwdBWgradArgs& k, int kindb, int kindw, dim3 grid, size_t lds, hipStream_t stream) {
+    const dim3 block(256);
+    // instances: phase B of block i-1 beside the weight gradients of block i, for the block sequences of the
+    // 256-point networks (encoder 0,1,2; decoder 3,4,5,6); anything else runs the generic pair
+#define RAAE_PAIR(KB_, KW_) if (kindb == KB_ && kindw == KW_) { \
+        raae::launch(block_bwd_b_wgrad_kernel<KB_, KW_>, block_bwd_b_wgrad_kernel_m<KB_, KW_>, grid, block, lds, stream, k); RAAE_LAUNCH_RET(); }
+    RAAE_PAIR(0, 1) RAAE_PAIR(1, 2) RAAE_PAIR(3, 4) RAAE_PAIR(4, 5) RAAE_PAIR(5, 6)
+    RAAE_PAIR(2, 3) RAAE_PAIR(6, 0)      // across the networks: encoder's last block beside decoder block 0's tasks, and back
+    RAAE_PAIR(6, -1)                     // the decoder's head conv (a lone generic task) beside its last block
+#undef RAAE_PAIR
+    raae::launch(block_bwd_b_wgrad_kernel<-1, -1>, block_bwd_b_wgrad_kernel_m<-1, -1>, grid, block, lds, stream, k);
+    RAAE_LAUNCH_RET();
+}
+
 extern "C" int raae_block_bwd_b_wgrad(const raae_block_bwd_b_t* bin, const raae_block_wgrad_t* win, int* nparts,
                                       int* nslab, void* stream) {
     static thread_local BwdBWgradArgs k;
@@ -1201,15 +1225,192 @@ extern "C" int raae_block_bwd_b_wgrad(const raae_block_bwd_b_t* bin, const raae_
     if (nparts) *nparts = gridb;
     k.nb = gridb;
     const size_t lds = ldsb > dynw ? ldsb : dynw;
-    const dim3 grid(gridb + total), block(256);
-    // instances: phase B of block i-1 beside the weight gradients of block i, for the block sequences of the
-    // 256-point networks (encoder 0,1,2; decoder 3,4,5,6); anything else runs the generic pair
-#define RAAE_PAIR(KB_, KW_) if (kindb == KB_ && kindw == KW_) { \
-        raae::launch(block_bwd_b_wgrad_kernel<KB_, KW_>, block_bwd_b_wgrad_kernel_m<KB_, KW_>, grid, block, lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); }
-    RAAE_PAIR(0, 1) RAAE_PAIR(1, 2) RAAE_PAIR(3, 4) RAAE_PAIR(4, 5) RAAE_PAIR(5, 6)
-    RAAE_PAIR(2, 3) RAAE_PAIR(6, 0)      // across the networks: encoder's last block beside decoder block 0's tasks, and back
-    RAAE_PAIR(6, -1)                     // the decoder's head conv (a lone generic task) beside its last block
-#undef RAAE_PAIR
-    raae::launch(block_bwd_b_wgrad_kernel<-1, -1>, block_bwd_b_wgrad_kernel_m<-1, -1>, grid, block, lds, (hipStream_t)stream, k);
+    return launch_bwd_b_wgrad(k, kindb, kindw, dim3(gridb + total), lds, (hipStream_t)stream);
+}
+
+// ---- two independent bodies of this translation unit in ONE launch (the general form of block_fwd_a2_kernel) ----
+// Workgroups [0, n1) run X::body, the rest Y::body; each body sees its index among, and the number of, the workgroups
+// that run it, so it computes what its own kernel computes.  X / Y are tags over the existing bodies.  Used across a
+// phase boundary of the 256-row step: the decoder backward that ends the mutual-information
+// phase carries the encoder's half of that phase's Adam update and then the encoder forward of the smoothness phase.
+#include "raae_adam_body.inc"
+#define COMMA ,
+template <int K> struct CoFwdA {
+    typedef BlockFwdAArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) { block_fwd_a_body<K>(a, bx, gx, dyn); }
+};
+template <int K> struct CoFwdB {
+    typedef BlockFwdBArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) { block_fwd_b_body<K>(a, bx, gx, dyn); }
+};
+template <int K> struct CoBwdA {
+    typedef BlockBwdAArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) { block_bwd_a_body<K, false>(a, bx, gx, dyn); }
+};
+template <int KB, int KW> struct CoBwdBW {      // the two bodies of block_bwd_b_wgrad_kernel<KB, KW>
+    typedef BwdBWgradArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) {
+        if (bx < a.nb) block_bwd_b_body<KB>(a.b, bx, a.nb, dyn);
+        else wgrad_multi_body<KW>(a.w, bx - a.nb, dyn);
+    }
+};
+template <bool CHK> struct CoAdam {             // adam_wide_kernel / adam_wide_chk_kernel (raae_optim.hip)
+    typedef AdamChkArgs Args;
+    static __device__ __forceinline__ void body(const Args& c, int bx, int gx, float*) {
+        const AdamArgs& a = c.a;
+        adam_wide_body<CHK>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
+                            c.nan_step, bx, gx);
+    }
+};
+template <class X, class Y> struct CoArgs { typename X::Args x; typename Y::Args y; int n1; };
+template <class X, class Y>
+__global__ __launch_bounds__(256) void co_kernel(CoArgs<X, Y> k) {
+    extern __shared__ __attribute__((aligned(16))) float dyn[];
+    const int n1 = k.n1;
+    if ((int)blockIdx.x < n1) {
+        __shared__ typename X::Args sx;
+        const typename X::Args& a = raae::args_to_lds_at(&sx, (int)offsetof(CoArgs<X COMMA Y>, x));
+        X::body(a, blockIdx.x, n1, dyn);
+    } else {
+        __shared__ typename Y::Args sy;
+        const typename Y::Args& a = raae::args_to_lds_at(&sy, (int)offsetof(CoArgs<X COMMA Y>, y));
+        Y::body(a, blockIdx.x - n1, gridDim.x - n1, dyn);
+    }
+}
+template <class X, class Y>
+__global__ __launch_bounds__(256) void co_kernel_m(const CoArgs<X, Y>* table) {      // one trial per grid plane
+    extern __shared__ __attribute__((aligned(16))) float dyn[];
+    const CoArgs<X, Y>* k = table + blockIdx.z;
+    const int n1 = k->n1;
+    if ((int)blockIdx.x < n1) {
+        __shared__ typename X::Args sx;
+        const typename X::Args& a = raae::args_from_ptr(&sx, &k->x);
+        X::body(a, blockIdx.x, n1, dyn);
+    } else {
+        __shared__ typename Y::Args sy;
+        const typename Y::Args& a = raae::args_from_ptr(&sy, &k->y);
+        Y::body(a, blockIdx.x - n1, gridDim.x - n1, dyn);
+    }
+}
+
+template <class X, class Y>
+static void co_go(const typename X::Args& x, const typename Y::Args& y, int g1, int g2, size_t lds, hipStream_t stream) {
+    static thread_local CoArgs<X, Y> k;
+    static_assert(sizeof(k) <= 4096, "kernel arguments (and the recorder's argument block) hold 4096 bytes");
+    k.x = x; k.y = y; k.n1 = g1;
+    raae::launch(co_kernel<X, Y>, co_kernel_m<X, Y>, dim3(g1 + g2), dim3(256), lds, stream, k);
+}
+
+// one side of raae_co_launch after its checks: the prepared argument block, geometry and instance
+struct CoSide {
+    int kind = -1, k = -1, kw = -1, grid = 0;
+    size_t lds = 0;
+    bool big = false, chk = false, wide = false;
+    int max_nslab = 0;
+    BlockFwdAArgs fa; BlockFwdBArgs fb; BlockBwdAArgs ba; BwdBWgradArgs bw; AdamChkArgs ad;
+};
+static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
+    RAAE_CHECK_ARG(args);
+    s.kind = kind;
+    int rc = 0;
+    switch (kind) {
+    case RAAE_CO_FWD_A:
+        rc = prep_block_fwd_a((const raae_block_fwd_a_t*)args, s.fa, s.grid, s.lds, s.k);
+        if (!rc) s.big = use_big(s.fa.B, s.k, kFamFwdA);
+        break;
+    case RAAE_CO_FWD_B:
+        rc = prep_block_fwd_b((const raae_block_fwd_b_t*)args, s.fb, s.grid, s.lds, s.k);
+        if (!rc) s.big = use_big(s.fb.B, s.k, kFamFwdB);
+        break;
+    case RAAE_CO_BWD_A:
+        rc = prep_block_bwd_a((const raae_block_bwd_a_t*)args, s.ba, s.grid, s.lds, s.k);
+        if (!rc) s.big = use_big(s.ba.B, s.k, kFamBwdA);
+        break;
+    case RAAE_CO_BWD_B_WGRAD: {
+        const raae_co_bwd_b_wgrad_t* p = (const raae_co_bwd_b_wgrad_t*)args;
+        RAAE_CHECK_ARG(p->b && p->w && p->nslab);
+        int gb, total;
+        size_t ldsb, dynw;
+        rc = prep_block_bwd_b(p->b, s.bw.b, gb, ldsb, s.k);
+        if (rc) return rc;
+        rc = prep_block_wgrad(p->w, p->nslab, s.bw.w, total, dynw, s.kw);
+        if (rc) return rc;
+        s.bw.nb = gb;
+        if (nparts) *nparts = gb;
+        s.grid = gb + total;
+        s.lds = ldsb > dynw ? ldsb : dynw;
+        s.big = p->b->B >= RAAE_BIG_ROWS;       // (raae_block_bwd_b_wgrad itself has no large-batch pairs)
+        return 0;
+    }
+    case RAAE_CO_ADAM: {
+        const raae_co_adam_t* p = (const raae_co_adam_t*)args;
+        RAAE_CHECK_ARG(p->p && p->m && p->v && p->g_slabs && p->seg_nslab && p->hyper && p->step && p->n > 0 &&
+                       (p->n % 64) == 0 && p->max_nslab >= 0 && (p->rule == RAAE_OPT_ADAM || p->rule == RAAE_OPT_ADAMW));
+        s.ad.a.p = p->p; s.ad.a.m = p->m; s.ad.a.v = p->v; s.ad.a.g_slabs = p->g_slabs; s.ad.a.slab_stride = p->slab_stride;
+        s.ad.a.seg_nslab = p->seg_nslab; s.ad.a.n = p->n; s.ad.a.hyper = p->hyper; s.ad.a.step = p->step;
+        s.ad.a.decoupled = p->rule == RAAE_OPT_ADAMW;
+        s.ad.nan_step = p->nan_step;
+        s.chk = p->nan_step != nullptr;
+        s.wide = p->max_nslab > 16;
+        s.max_nslab = p->max_nslab;
+        long g = (p->n + 31) / 32;              // adam_wide_kernel's geometry (raae_adam_step)
+        if (g > 4096) g = 4096;
+        s.grid = (int)g; s.lds = 0;
+        return 0;
+    }
+    default:
+        return RAAE_EINVAL;
+    }
+    if (!rc && nparts) *nparts = s.grid;
+    return rc;
+}
+// a side on its own: the launch its own entry point makes
+static int co_single(const CoSide& s, hipStream_t stream) {
+    const int kind = s.k;
+    const bool big = s.big;
+    switch (s.kind) {
+    case RAAE_CO_FWD_A: { const raae_block_fwd_a_t& a = s.fa; RAAE_LAUNCH_KIND_BIG(block_fwd_a_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
+    case RAAE_CO_FWD_B: { const raae_block_fwd_b_t& a = s.fb; RAAE_LAUNCH_KIND_BIG(block_fwd_b_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
+    case RAAE_CO_BWD_A: { const raae_block_bwd_a_t& a = s.ba; RAAE_LAUNCH_KIND_BIG(block_bwd_a_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
+    case RAAE_CO_BWD_B_WGRAD: return launch_bwd_b_wgrad(s.bw, s.k, s.kw, dim3(s.grid), s.lds, stream);
+    default: {
+        const AdamArgs& a = s.ad.a;
+        if (s.chk) return raae_optim_step_chk(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n,
+                                              a.decoupled ? RAAE_OPT_ADAMW : RAAE_OPT_ADAM, a.hyper, a.step, s.max_nslab,
+                                              s.ad.nan_step, stream);
+        return raae_adam_step(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
+                              s.max_nslab, stream);
+    }
+    }
     RAAE_LAUNCH_RET();
 }
+
+extern "C" int raae_co_launch(int kind_x, const void* args_x, int kind_y, const void* args_y, int* nparts_x,
+                              int* nparts_y, void* stream) {
+    static thread_local CoSide x, y;
+    int rc = co_prep(kind_x, args_x, nparts_x, x);
+    if (rc) return rc;
+    rc = co_prep(kind_y, args_y, nparts_y, y);
+    if (rc) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const size_t lds = x.lds > y.lds ? x.lds : y.lds;
+    if (!x.big && !y.big) {
+        // instances: what the decoder backward of the 256-point networks (blocks 6, 5, 4, 3) meets when the encoder's
+        // Adam half and then the encoder forward (blocks 0, 1, 2) ride in it; anything else: two launches
+#define RAAE_CO(XK, XCOND, XT, XF, YK, YCOND, YT, YF) if (x.kind == XK && (XCOND) && y.kind == YK && (YCOND)) { \
+            co_go<XT, YT>(x.XF, y.YF, x.grid, y.grid, lds, st); RAAE_LAUNCH_RET(); }
+        RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
+        RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
+        RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 5 && x.kw == 6, CoBwdBW<5 COMMA 6>, bw, RAAE_CO_FWD_A, y.k == 0, CoFwdA<0>, fa)
+        RAAE_CO(RAAE_CO_BWD_A, x.k == 5, CoBwdA<5>, ba, RAAE_CO_FWD_B, y.k == 0, CoFwdB<0>, fb)
+        RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 4 && x.kw == 5, CoBwdBW<4 COMMA 5>, bw, RAAE_CO_FWD_A, y.k == 1, CoFwdA<1>, fa)
+        RAAE_CO(RAAE_CO_BWD_A, x.k == 4, CoBwdA<4>, ba, RAAE_CO_FWD_B, y.k == 1, CoFwdB<1>, fb)
+        RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 3 && x.kw == 4, CoBwdBW<3 COMMA 4>, bw, RAAE_CO_FWD_A, y.k == 2, CoFwdA<2>, fa)
+        RAAE_CO(RAAE_CO_BWD_A, x.k == 3, CoBwdA<3>, ba, RAAE_CO_FWD_B, y.k == 2, CoFwdB<2>, fb)
+#undef RAAE_CO
+    }
+    rc = co_single(x, st);
+    if (rc) return rc;
+    return co_single(y, st);
+}
+#undef COMMA

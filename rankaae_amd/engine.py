@@ -901,15 +901,26 @@ class StepEngine:
         return P
 
     # -- emit the step program (eagerly or under capture)
-    def _adam(self, P, name, notes_host):
+    def _adam(self, P, name, notes_host, part=None, ride=False):
+        """The update of optimizer ``name``.  ``part`` ("enc" / "dec"): only that network's slice of the optimizer's
+        range (the rules are element-wise, the step count is advanced by the step's head, and both halves get the whole
+        range's slab hint, so the two halves together are bit for bit the one launch); ``ride``: do not launch, return
+        the ``("adam", launch)`` item for ``CompactNet.lockstep``."""
         o = self.opts[name]
         if notes_host is not None:
             P.seg[name].copy_(torch.from_numpy(notes_host))
-            P.max_slab[name] = int(notes_host.max())      # host-side hint for the Adam kernel's lane split
+            if part is None or part == "dec":     # (a first half sees only its own network's counts: _cross_ready)
+                P.max_slab[name] = int(notes_host.max())      # host-side hint for the Adam kernel's lane split
         self.join_side_streams()
         if self.phase_hook is not None:      # debugging / parity tests: gradients before the update
             self._host_hook(self.phase_hook, name, P)
         lo, n = o.lo, o.hi - o.lo
+        if part is not None:
+            r0, r1 = self.arena.ranges[part]
+            lo, hi = max(o.lo, r0), min(o.hi, r1)
+            n = hi - lo
+            assert n > 0 and lo % 64 == 0 and n % 64 == 0 and self.world_size == 1
+        m, v = o.m[lo - o.lo:], o.v[lo - o.lo:]
         if self.world_size > 1:
             # flat gradient -> RCCL mean over ranks -> Adam on the averaged single slab
             ops.slab_reduce(self.G[0, lo:], self.arena.n, P.seg[name][lo // 64:], n, self.G_flat[lo:], P.max_slab[name])
@@ -917,15 +928,27 @@ class StepEngine:
             g, seg, max_slab = self.G_flat[lo:], self.seg_ones[lo // 64:], 1
         else:
             g, seg, max_slab = self.G[0, lo:], P.seg[name][lo // 64:], P.max_slab[name]
-        if self.detect_anomaly:     # the same update by the checked twins of its kernels (all four rules)
-            ops.optim_step(self.arena.P[lo:], o.m, o.v, g, self.arena.n, seg, n, o.rule, o.hyper,
-                           self.steps_dev[o.index:], max_slab, nan_step=self.nan_flags[o.index:o.index + 1])
-        elif o.rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW):
-            ops.adam_step(self.arena.P[lo:], o.m, o.v, g, self.arena.n, seg, n, o.hyper, self.steps_dev[o.index:],
-                          self.decoupled, max_slab)
-        else:           # RAdam / AdaBound: raae_optim_step, same arena, slabs and step count
-            ops.optim_step(self.arena.P[lo:], o.m, o.v, g, self.arena.n, seg, n, o.rule, o.hyper,
-                           self.steps_dev[o.index:], max_slab)
+        if part is not None and notes_host is not None and part != "dec":
+            max_slab = max(max_slab, int(notes_host[lo // 64:(lo + n) // 64].max()))
+        nan = self.nan_flags[o.index:o.index + 1] if self.detect_anomaly else None
+
+        def launch():
+            if self.detect_anomaly:     # the same update by the checked twins of its kernels (all four rules)
+                ops.optim_step(self.arena.P[lo:], m, v, g, self.arena.n, seg, n, o.rule, o.hyper,
+                               self.steps_dev[o.index:], max_slab, nan_step=nan)
+            elif o.rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW):
+                ops.adam_step(self.arena.P[lo:], m, v, g, self.arena.n, seg, n, o.hyper, self.steps_dev[o.index:],
+                              self.decoupled, max_slab)
+            else:           # RAdam / AdaBound: raae_optim_step, same arena, slabs and step count
+                ops.optim_step(self.arena.P[lo:], m, v, g, self.arena.n, seg, n, o.rule, o.hyper,
+                               self.steps_dev[o.index:], max_slab)
+        if ride:
+            # the Adam rules have a body in the conv kernels' translation unit (raae_co_launch); RAdam / AdaBound go alone
+            launch.co_args = (ops.adam_part_args(self.arena.P[lo:], m, v, g, self.arena.n, seg, n, o.rule, o.hyper,
+                                                 self.steps_dev[o.index:], max_slab, nan)
+                              if o.rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW) else None)
+            return ("adam", launch)
+        launch()
         if self.post_phase_hook is not None:  # parity tests: teacher forcing at phase granularity
             self._host_hook(self.post_phase_hook, name, P)
 
@@ -1118,15 +1141,45 @@ class StepEngine:
         will_backprop()
         ops.mse_fwd_bwd(z_rec, z_s, b * ns, P.lpart, P.dstyles, fin=(1.0, lo, 3, 5, P.ticket))
         left = enc.backward(E, out, P.m_enc[4], P.dstyles, P.dspec, keep_pending=True)
-        dec.backward(D, z_s, P.m_dec[2], P.dspec, None, pending=left)
-        self._adam(P, "mutual_info", self._slab_notes)
+        # Across the phase boundary (build-only key `pair_across_phases`, default on; serial chain of the fused conv
+        # networks only): the smoothness phase's encoder forward reads encoder state only, this phase's decoder backward
+        # decoder state only.  Once the decoder's first block launch has carried the encoder's last weight-gradient tasks,
+        # the encoder's half of this phase's update and then the encoder forward ride in the decoder backward's launches
+        # (CompactNet.lockstep); the decoder's half of the update follows.  Same kernels' bodies on the same operands:
+        # bit for bit the serial order (tests/test_cross_phase_gpu.py).
+        cross = (pair and smooth and not defer and not self.defer_tail and left is not None and self.world_size == 1 and
+                 bool(c.get("pair_across_phases", True)) and self.phase_hook is None and
+                 self.post_phase_hook is None and hasattr(dec, "backward_steps"))
+        styles_e = None
+        if cross:
+            steps = dec.backward_steps(D, z_s, P.m_dec[2], P.dspec, None, pending=left)
+            first = next(steps)                  # (the head's backward has been launched inline)
+            first = steps.send(ops.launch_item(first[0], first[1]))      # block_bwd_b_wgrad: the encoder's gradients are complete
+            # Both halves must choose the kernel one launch over the range would: that needs more than 16 slabs somewhere
+            # in the ENCODER's slice already (the decoder's counts are not all known on the first, eager emission)
+            if record:
+                r0, r1 = self.arena.ranges["enc"]
+                P.cross_ok = int(self._slab_notes[r0 // 64:r1 // 64].max()) > 16
+            if getattr(P, "cross_ok", False):
+                def rider():
+                    yield self._adam(P, "mutual_info", self._slab_notes, part="enc", ride=True)
+                    return (yield from enc.forward_steps(E, P.spec, P.m_enc[5]))
+                _, styles_e = enc.lockstep(steps, rider(), first)
+                self._adam(P, "mutual_info", self._slab_notes, part="dec")
+            else:
+                enc.drive(steps, first)
+                self._adam(P, "mutual_info", self._slab_notes)
+        else:
+            dec.backward(D, z_s, P.m_dec[2], P.dspec, None, pending=left)
+            self._adam(P, "mutual_info", self._slab_notes)
         # ---- phase E: smoothness (:189-200); encoder gradients are discarded by the reference
         if smooth and defer:
             styles = enc.forward(E, P.spec, P.m_enc[5])        # (its gradients are discarded: no backward)
             ops.tail_prepare(styles, P.styles_tail, b * ns, self.steps_dev[4:], self.rng_state, self.tail_state[parity & 1])
         elif smooth:
             self._begin_phase(record)
-            styles = enc.forward(E, P.spec, P.m_enc[5])        # (its gradients are discarded: no backward)
+            # (its gradients are discarded: no backward; `styles_e`: it has already run, beside phase D's decoder backward)
+            styles = styles_e if styles_e is not None else enc.forward(E, P.spec, P.m_enc[5])
             will_backprop(dec)
             out = dec.forward(D, styles, P.m_dec[3])
             will_backprop()

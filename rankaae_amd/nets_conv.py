@@ -290,6 +290,52 @@ class CompactNet:
     def backward(self, ws, x, masks, g_out, dx_in=None, pending=None, keep_pending=False):
         """``pending``: weight-gradient tasks another network's backward left over (its return value with
         ``keep_pending``): they ride in this network's first fused launch instead of a launch of their own."""
+        return self.drive(self.backward_steps(ws, x, masks, g_out, dx_in, pending, keep_pending))
+
+    @staticmethod
+    def drive(steps, first=None):
+        """Run a generator of launches (``forward_steps`` / ``backward_steps``) to its end, every launch on its own;
+        ``first``: the item it has already yielded.  Returns the generator's result."""
+        try:
+            item = next(steps) if first is None else first
+            while True:
+                item = steps.send(ops.launch_item(item[0], item[1]))
+        except StopIteration as done:
+            return done.value
+
+    @staticmethod
+    def lockstep(main, rider, first=None):
+        """Two independent generators of launches in lockstep: while both have a launch ready that the two-body
+        launch takes (``ops.co_pairable``: ``main`` a backward pass, ``rider`` whatever may run beside it) the two share
+        one launch (raae_co_launch); a launch of ``main`` that takes no rider goes alone, and whichever generator
+        outlives the other runs the rest alone.  ``first``: the item ``main`` has already yielded.  Returns the two results."""
+        gens, cur, out = [main, rider], [first, None], [None, None]
+
+        def advance(j, n, start=False):
+            try:
+                cur[j] = next(gens[j]) if start else gens[j].send(n)
+            except StopIteration as done:
+                out[j], gens[j], cur[j] = done.value, None, None
+        if first is None:
+            advance(0, None, True)
+        advance(1, None, True)
+        while gens[0] is not None or gens[1] is not None:
+            if gens[0] is not None and gens[1] is not None:
+                if ops.co_pairable(cur[0][0], cur[0][1], cur[1][0], cur[1][1]):
+                    n1, n2 = ops.co_launch(cur[0][0], cur[0][1], cur[1][0], cur[1][1])
+                    advance(1, n2)       # (the rider first: what it launches inline next must not wait for `main`'s host work)
+                    advance(0, n1)
+                    continue
+                j = 1 if cur[1][0] == "adam" else 0      # (an update that cannot ride goes first: the rest waits for it)
+            else:
+                j = 0 if gens[0] is not None else 1
+            advance(j, ops.launch_item(cur[j][0], cur[j][1]))
+        return out[0], out[1]
+
+    def backward_steps(self, ws, x, masks, g_out, dx_in=None, pending=None, keep_pending=False):
+        """Generator form of the backward pass: yields ``(kind, argument block)`` at every launch of the fused block
+        kernels on the main chain ("bwd_b", "bwd_a", and "wgrad" for weight-gradient tasks that end the pass) and expects
+        back what the launch returns (``ops.launch_item``); everything else is launched inline."""
         eng, b = self.eng, ws.b
         G = eng.gslab
         last, wl = self.blocks[-1], ws.blk[-1]
@@ -332,10 +378,6 @@ class CompactNet:
             for (_, _, _, _, _, mod), n_ in zip(lins_, ns[len(convs_):]):
                 eng.note_slabs([mod.weight, mod.bias], n_)
 
-        def flush(pend):
-            if pend is not None:
-                note_wgrad(pend, ops.block_wgrad(b, None, None, eng.arena.n, args=pend[0]))
-            return None
 
         forked = []          # branched graph: blocks whose weight-gradient launches wait for the next fork
 
@@ -370,13 +412,13 @@ class CompactNet:
                 bne = self._bn(m.bn_excit, w.pE2, w.nE2, b * k.Lout, True, False) if k.cve is not None else None
                 ve2 = ops.make_view(w.E2, m.relu_excit_2.weight, bne)
                 if pending is not None:
-                    nB, ns_w = ops.block_bwd_b(gspec(None, None), v1, ve2 if k.cve is not None else None, b, k, m, w,
-                                               eng.arena.n, G, wgrad=pending[0])
+                    nB, ns_w = yield ("bwd_b", ops.block_bwd_b_args(gspec(None, None), v1, ve2 if k.cve is not None else None,
+                                                                    b, k, m, w, eng.arena.n, G, wgrad=pending[0]))
                     note_wgrad(pending, ns_w)
                     pending = None
                 else:
-                    nB = ops.block_bwd_b(gspec(None, None), v1, ve2 if k.cve is not None else None, b, k, m, w,
-                                         eng.arena.n, G)
+                    nB = yield ("bwd_b", ops.block_bwd_b_args(gspec(None, None), v1, ve2 if k.cve is not None else None,
+                                                              b, k, m, w, eng.arena.n, G))
                 eng.note_slabs([m.relu2.weight] + ([m.relu_short.weight] if k.cvs is not None else []) +
                                [m.relu_excit_3.weight if k.cve is not None else m.relu_excit_2.weight], nB)
                 g1 = ops.make_grad(w.dBn2, raw=w.T1, slope=m.relu1.weight, bn=bn2v, g_partials=w.pdBn2, g_nparts=nB)
@@ -384,8 +426,9 @@ class CompactNet:
                                    g_nparts=nB) if k.cve is not None else None
                 dE2 = w.dE2 if k.cve is not None else w.dEx
                 mask = self._mask(masks, i, True)
-                w.ndR = ops.block_bwd_a(g1, ge, vR(), mask, b, k, m, w, dE2, dR if need_dx else None,
-                                        w.pdR if (need_dx and m.bn1 is not None) else None, eng.arena.n, G)
+                w.ndR = yield ("bwd_a", ops.block_bwd_a_args(g1, ge, vR(), mask, b, k, m, w, dE2, dR if need_dx else None,
+                                                             w.pdR if (need_dx and m.bn1 is not None) else None,
+                                                             eng.arena.n, G))
                 eng.note_slabs([m.relu1.weight, m.relu_excit_1.weight] +
                                ([m.relu_excit_2.weight] if k.cve is not None else []), w.ndR)
                 # weight gradients from the materialised gradients (side streams; no BatchNorm prologue).
@@ -434,7 +477,9 @@ class CompactNet:
                         gy = dict(g=w.dR, bn=None, parts=None, nparts=0)
                 continue
             # ---- main branch
-            pending = flush(pending)
+            if pending is not None:
+                note_wgrad(pending, (yield ("wgrad", pending[0])))
+                pending = None
             go2 = gspec(w.T2, m.relu2.weight)
             v1 = ops.make_view(w.T1, m.relu1.weight, self._bn(m.bn2, w.pT1, w.nT1, b * k.L1, True, False))
             self._cw(go2, b, k.cv2, v1, m.conv2, m.relu2)
@@ -480,5 +525,6 @@ class CompactNet:
         fork_wgrad()
         if keep_pending:
             return pending
-        flush(pending)
+        if pending is not None:
+            note_wgrad(pending, (yield ("wgrad", pending[0])))
         return None

@@ -697,8 +697,9 @@ def block_fwd_b(a):
     return _probed("block_fwd_b_kernel", a.nbytes, launch, a.tag)
 
 
-def block_bwd_b(gy, vT1, vE2, B, k, m, w, slab_stride, gslab, wgrad=None):
-    """Fused backward phase B (``w``: the block's workspace, ``gslab(p)``: slab-0 view of parameter p)."""
+def block_bwd_b_args(gy, vT1, vE2, B, k, m, w, slab_stride, gslab, wgrad=None):
+    """``raae_block_bwd_b_t`` of fused backward phase B (``w``: the block's workspace, ``gslab(p)``: slab-0 view of
+    parameter p); ``wgrad``: the following block's weight-gradient tasks, which ride in the same launch."""
     a = _lib.BlockBwdBT()
     a.gy, a.vT1 = gy, vT1
     if vE2 is not None:
@@ -721,23 +722,37 @@ def block_bwd_b(gy, vT1, vE2, B, k, m, w, slab_stride, gslab, wgrad=None):
     a.dT2, a.dSh, a.dEx, a.dBn2, a.pdBn2 = _p(w.dT2), _p(w.dSh), _p(w.dEx), _p(w.dBn2), _p(w.pdBn2)
     a.dslope2 = _p(gslab(m.relu2.weight))
     a.slab_stride = slab_stride
-    nbytes = block_bytes("bwd_b", k, B, input_bn=bool(gy.has_bn))
+    a.nbytes = block_bytes("bwd_b", k, B, input_bn=bool(gy.has_bn))
+    a.wgrad, a.tag = wgrad, _ktag(k)
+    a.keep = (gy, vT1, vE2)         # (what the struct's pointers refer to stays alive as long as the struct)
+    return a
+
+
+def block_bwd_b_launch(a):
+    """Launch a ``block_bwd_b_args`` block; returns the partial-row count, with weight-gradient tasks
+    ``(rows, [slabs per task])``."""
+    wgrad, nbytes = a.wgrad, a.nbytes
     if wgrad is not None:          # the following block's weight-gradient tasks ride in the same launch
         def launch2():
             n, ns = C.c_int(0), (C.c_int * 6)()
             check(_lib.load().raae_block_bwd_b_wgrad(C.byref(a), C.byref(wgrad), C.byref(n), ns, _stream()),
                   "raae_block_bwd_b_wgrad")
             return n.value, list(ns)[:wgrad.n_conv + wgrad.n_lin]
-        return _probed("block_bwd_b_wgrad_kernel", nbytes + wgrad.nbytes, launch2, _ktag(k))
+        return _probed("block_bwd_b_wgrad_kernel", nbytes + wgrad.nbytes, launch2, a.tag)
 
     def launch():
         n = C.c_int(0)
         check(_lib.load().raae_block_bwd_b(C.byref(a), C.byref(n), _stream()), "raae_block_bwd_b")
         return n.value
-    return _probed("block_bwd_b_kernel", nbytes, launch, _ktag(k))
+    return _probed("block_bwd_b_kernel", nbytes, launch, a.tag)
 
 
-def block_bwd_a(g1, ge, view_in, mask, B, k, m, w, dE2, dR, pdR, slab_stride, gslab):
+def block_bwd_b(gy, vT1, vE2, B, k, m, w, slab_stride, gslab, wgrad=None):
+    """Fused backward phase B, launched."""
+    return block_bwd_b_launch(block_bwd_b_args(gy, vT1, vE2, B, k, m, w, slab_stride, gslab, wgrad))
+
+
+def block_bwd_a_args(g1, ge, view_in, mask, B, k, m, w, dE2, dR, pdR, slab_stride, gslab):
     a = _lib.BlockBwdAT()
     a.g1 = g1
     if ge is not None:
@@ -758,12 +773,82 @@ def block_bwd_a(g1, ge, view_in, mask, B, k, m, w, dE2, dR, pdR, slab_stride, gs
         a.dslope_e2 = _p(gslab(m.relu_excit_2.weight))
     a.slab_stride = slab_stride
 
+    a.nbytes = block_bytes("bwd_a", k, B, mask=mask is not None, need_dx=dR is not None, input_bn=pdR is not None)
+    a.tag = _ktag(k)
+    a.keep = (g1, ge, view_in)
+    return a
+
+
+def block_bwd_a_launch(a):
     def launch():
         n = C.c_int(0)
         check(_lib.load().raae_block_bwd_a(C.byref(a), C.byref(n), _stream()), "raae_block_bwd_a")
         return n.value
-    return _probed("block_bwd_a_kernel", block_bytes("bwd_a", k, B, mask=mask is not None, need_dx=dR is not None,
-                                                     input_bn=pdR is not None), launch, _ktag(k))
+    return _probed("block_bwd_a_kernel", a.nbytes, launch, a.tag)
+
+
+def block_bwd_a(g1, ge, view_in, mask, B, k, m, w, dE2, dR, pdR, slab_stride, gslab):
+    return block_bwd_a_launch(block_bwd_a_args(g1, ge, view_in, mask, B, k, m, w, dE2, dR, pdR, slab_stride, gslab))
+
+
+def adam_part_args(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab, nan_step=None):
+    """``raae_co_adam_t``: an Adam / AdamW update (of a slice of an optimizer's range) as a body of ``co_launch``."""
+    a = _lib.CoAdamT()
+    a.p, a.m, a.v, a.g_slabs, a.slab_stride = _ptr(p), _ptr(m), _ptr(v), _ptr(g_slabs), slab_stride
+    a.seg_nslab, a.n, a.rule = _ptr(seg_nslab, torch.int16), n, int(rule)
+    a.hyper, a.step, a.max_nslab = _ptr(hyper, torch.float64), _ptr(step, torch.int32), int(max_nslab)
+    a.nan_step = _ptr(nan_step, torch.int32) if nan_step is not None else None
+    a.nbytes = 28 * n
+    return a
+
+
+# what a generator of launches (nets_conv.forward_steps / backward_steps, the engine's Adam halves) yields as its first
+# two items: ("a" | "b" | "bwd_a" | "bwd_b" | "wgrad" | "adam", argument block)
+_CO_KIND = {"a": _lib.CO_FWD_A, "b": _lib.CO_FWD_B, "bwd_a": _lib.CO_BWD_A, "adam": _lib.CO_ADAM}
+
+
+def launch_item(kind, a):
+    """One yielded launch on its own; returns what the generator expects back."""
+    if kind == "a":
+        return block_fwd_a(a)
+    if kind == "b":
+        return block_fwd_b(a)
+    if kind == "bwd_a":
+        return block_bwd_a_launch(a)
+    if kind == "bwd_b":
+        return block_bwd_b_launch(a)
+    if kind == "wgrad":
+        return block_wgrad(a.B, None, None, a.slab_stride, args=a)
+    if kind == "adam":
+        return a()            # (the engine's own launch: any rule, checked or not)
+    raise ValueError(kind)
+
+
+def co_pairable(kx, ax, ky, ay):
+    """Whether ``co_launch`` takes the two yielded launches (x: a backward launch, y: the rider)."""
+    return ((kx == "bwd_a" or (kx == "bwd_b" and ax.wgrad is not None)) and
+            (ky in ("a", "b") or (ky == "adam" and getattr(ay, "co_args", None) is not None)))
+
+
+def co_launch(kx, ax, ky, ay):
+    """Two independent launches as one (``raae_co_launch``); returns what each would have returned alone."""
+    ns = (C.c_int * 6)()
+    if kx == "bwd_b":
+        wgrad = ax.wgrad
+        px = _lib.CoBwdBWgradT(C.pointer(ax), C.pointer(wgrad), C.cast(ns, C.POINTER(C.c_int)))
+        cx, nbx, fam = _lib.CO_BWD_B_WGRAD, ax.nbytes + wgrad.nbytes, "bwd_b_wgrad"
+    else:
+        px, cx, nbx, fam = ax, _CO_KIND[kx], ax.nbytes, kx
+    py = ay.co_args if ky == "adam" else ay
+
+    def launch():
+        n1, n2 = C.c_int(0), C.c_int(0)
+        check(_lib.load().raae_co_launch(cx, C.cast(C.pointer(px), C.c_void_p), _CO_KIND[ky],
+                                         C.cast(C.pointer(py), C.c_void_p), C.byref(n1), C.byref(n2), _stream()),
+              "raae_co_launch")
+        rx = (n1.value, list(ns)[:ax.wgrad.n_conv + ax.wgrad.n_lin]) if kx == "bwd_b" else n1.value
+        return rx, (None if ky == "adam" else n2.value)
+    return _probed(f"co_kernel[{fam}+{'fwd_' + ky if ky in ('a', 'b') else ky}]", nbx + py.nbytes, launch)
 
 
 def block_wgrad_args(B, conv_tasks, lin_tasks, slab_stride):
