@@ -192,6 +192,28 @@ int raae_style_metrics(const float* z, int n, int k, const double* a_coef, doubl
  * sweeps (sc/report/analysis.py:78-86, `decoder(con_c).reshape(n_spec, n_sampling, L).mean(axis=1)`). */
 int raae_group_mean(const float* x, int groups, int per, int L, float* out, void* stream);
 
+/* Model-selection scores of one trained model (ABI 21): what the reference's report step computes per trial with scipy
+ * and scikit-learn on host copies (sc/report/analysis.py:394-450, evaluate_model), unrounded, where the validation
+ * styles and spectra already are.  styles [n][k] fp32; aux [n][n_aux] float64 descriptors (n_aux <= k); spec_in /
+ * spec_out [n][L] fp32; thresh: the n_thresh float64 thresholds of the coordination-number sweeps (the reference's
+ * np.linspace(-3.5, 3.5, 700); read only when n_aux >= 2); work: raae_select_work_bytes(n, k, n_aux, n_thresh) bytes.
+ * out, RAAE_SEL_HEAD + RAAE_SEL_STRIDE * n_aux doubles:
+ *   [0] mean and [1] population std of the per-spectrum MAE; [2] max_i |spearman(style_i, style_{k-1})|, i < k - 1;
+ *   descriptor i != 1 at RAAE_SEL_HEAD + RAAE_SEL_STRIDE * i (x = descriptor, y = style i, the argument order
+ *   evaluate_model really uses): Spearman, linregress slope, intercept, r^2, the degree-2 fit's coefficients in the
+ *   unscaled basis (c0, c1, c2), SSE / n, r^2 of the fitted values against the style;
+ *   descriptor 1 (coordination number, get_confusion_matrix): valid (0: more than three distinct classes, the
+ *   reference's None), support-weighted F1, the indices of the two arg-max thresholds in `thresh`, their values, and the
+ *   3x3 confusion matrix [true class 0..2][predicted], row major.
+ * Every launch has the one-model-per-grid-plane form: J recorded calls replay as one gridDim.z = J sequence
+ * (raae_record_* / raae_multi_*).  No atomics: a replay is bitwise repeatable.  Inputs must be finite. */
+#define RAAE_SEL_HEAD 4
+#define RAAE_SEL_STRIDE 16
+long raae_select_work_bytes(int n, int k, int n_aux, int n_thresh);
+int raae_select_scores(const float* styles, int n, int k, const double* aux, int n_aux, const float* spec_in,
+                       const float* spec_out, int L, const double* thresh, int n_thresh, void* work, double* out,
+                       void* stream);
+
 /* The adversarial branch of a step in ONE launch (DiscriminatorFC with three layers of width `hidden` = 64 and
  * nstyle <= 16; sc/clustering/model.py:631-663, sc/utils/functions.py:109-132, model.py:8-22): input = [z_real ;
  * styles] (+ sigma * noise), Linear/PReLU/Dropout x2, Linear, BCE-with-logits against ones (real rows) and zeros (fake
@@ -582,7 +604,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 20
+#define RAAE_ABI_VERSION 21
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -9,11 +9,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librankaae_hip.so")
 
 RAAE_MAX_PARTS = 512
-ABI_VERSION = 20
+ABI_VERSION = 21
 IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP = 0, 1, 2
 OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS, OUT_RELU = 0, 1, 2, 3, 4
 G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU = 0, 1, 2, 3, 4
 OPT_ADAM, OPT_ADAMW, OPT_RADAM, OPT_ADABOUND = 0, 1, 2, 3     # raae_optim_step rules
+SEL_HEAD, SEL_STRIDE = 4, 16         # RAAE_SEL_*: layout of raae_select_scores' output block
 
 
 class BnT(C.Structure):
@@ -195,6 +196,8 @@ SIGNATURES = {
     "raae_rank_rows_finish": (_I, [_P, _I, _I, _I, _I, C.c_float, _P, _P, _P, _I, _P]),
     "raae_style_metrics": (_I, [_P, _I, _I, _P, _P, _P, _P]),
     "raae_group_mean": (_I, [_P, _I, _I, _I, _P, _P]),
+    "raae_select_work_bytes": (_L, [_I, _I, _I, _I]),
+    "raae_select_scores": (_I, [_P, _I, _I, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P]),
     "raae_recon_loss_fwd_bwd": (_I, [_P, _P, _I, _I, _I, _P, _PI, _P, C.POINTER(LossFinT), _P]),
     "raae_smooth_loss_fwd_bwd": (_I, [_P, _I, _I, C.POINTER(C.c_float), _I, _P, _PI, _P, C.POINTER(LossFinT), _P]),
     "raae_mse_fwd_bwd": (_I, [_P, _P, _L, _P, _PI, _P, C.POINTER(LossFinT), _P]),

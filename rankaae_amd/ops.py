@@ -233,6 +233,21 @@ def group_mean(x, groups, per, L, out):
     check(_lib.load().raae_group_mean(_ptr(x), groups, per, L, _ptr(out), _stream()), "raae_group_mean")
 
 
+def select_work_bytes(n, k, n_aux, n_thresh):
+    return int(_lib.load().raae_select_work_bytes(n, k, n_aux, n_thresh))
+
+
+def select_scores(styles, n, k, aux, n_aux, spec_in, spec_out, L, thresh, work, out):
+    """Model-selection scores of one model (``raae_select_scores``): ``aux`` and ``thresh`` float64, ``out`` float64
+    ``[SEL_HEAD + SEL_STRIDE * n_aux]``, ``work`` a byte buffer of ``select_work_bytes``."""
+    assert out.numel() >= _lib.SEL_HEAD + _lib.SEL_STRIDE * n_aux
+    assert work.numel() * work.element_size() >= select_work_bytes(n, k, n_aux, thresh.numel())
+    assert styles.numel() == n * k and aux.numel() == n * n_aux and spec_in.numel() == n * L and spec_out.numel() == n * L
+    check(_lib.load().raae_select_scores(_ptr(styles), n, k, _ptr(aux, torch.float64), n_aux, _ptr(spec_in),
+                                         _ptr(spec_out), L, _ptr(thresh, torch.float64), thresh.numel(), _ptr(work, None),
+                                         _ptr(out, torch.float64), _stream()), "raae_select_scores")
+
+
 def _fin(fin):
     """``fin = (scale, out, slot, acc_slot, ticket)``: the loss is finished inside the kernel (``raae_loss_fin_t``);
     None: the partials are left for ``loss_finalize``."""

@@ -40,3 +40,34 @@ def write_csv(path, spec, aux, grid):
         for i in range(n):
             row = [f"mp-{i}", "0"] + [repr(float(v)) for v in aux[i]] + [repr(float(v)) for v in spec[i]]
             f.write(",".join(row) + "\n")
+
+
+def selection_inputs(seed, n_jobs, n_rows, nstyle=6, n_aux=5, n_points=32, four_class_job=None):
+    """Inputs of the model-selection scores for ``n_jobs`` pretend models, reproducible from ``seed`` alone (the fixture
+    ``tests/golden/selection_ref.json`` stores only their SHA-256): per job ``(styles [n, nstyle] f32, aux [n, n_aux]
+    f64, spec_in [n, L] f32, spec_out [n, L] f32)``.  Descriptors are standard normal, column 1 drawn from {4, 5, 6};
+    style i follows descriptor i (with a quadratic term) plus noise whose size differs per job, the remaining styles
+    follow style 0 weakly, ``spec_out = spec_in + noise``.  Job ``four_class_job`` gets a coordination-number column
+    drawn from {4, 5, 6, 7}: the case the reference's ``get_confusion_matrix`` answers with ``None``."""
+    rng = np.random.default_rng(seed)
+    d = rng.standard_normal((n_rows, n_aux))
+    if n_aux > 1:
+        d[:, 1] = rng.integers(4, 7, size=n_rows)
+    spec_in = (0.5 + 0.5 * rng.random((n_rows, n_points))).astype(np.float32)
+    jobs = []
+    for j in range(n_jobs):
+        sigma = 0.25 + 0.9 * rng.random()
+        aux = d.copy()
+        if j == four_class_job:
+            aux[:, 1] = rng.integers(4, 8, size=n_rows)
+        z = rng.standard_normal((n_rows, nstyle))
+        for i in range(min(n_aux, nstyle)):
+            x = (aux[:, i] - 5.0) * 1.3 if i == 1 else aux[:, i]
+            sign = -1.0 if (i + j) % 3 == 0 and i != 1 else 1.0
+            z[:, i] = sign * (x + 0.15 * x * x) + sigma * (0.6 + 0.2 * i) * z[:, i]
+        for i in range(n_aux, nstyle):
+            z[:, i] = z[:, i] + (0.1 + 0.5 * rng.random()) * z[:, 0]
+        noise = (0.01 + 0.05 * rng.random()) * rng.standard_normal((n_rows, n_points))
+        spec_out = (spec_in + noise * (0.5 + rng.random((n_rows, 1)))).astype(np.float32)
+        jobs.append((z.astype(np.float32), aux, spec_in, spec_out))
+    return jobs
