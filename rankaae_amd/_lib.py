@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librankaae_hip.so")
 
 RAAE_MAX_PARTS = 512
-ABI_VERSION = 21
+ABI_VERSION = 22
 IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP = 0, 1, 2
 OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS, OUT_RELU = 0, 1, 2, 3, 4
 G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU = 0, 1, 2, 3, 4
@@ -187,7 +187,6 @@ SIGNATURES = {
     "raae_dense_bwd_st": (_I, [_P, _I, _P, _I, _P, _P, _PB, _I, _I, _P, _I, _I, _P, _PB, _P, _P,
                                _P, _P, _P, _L, _PI, _P, _P, _I, _P]),
     "raae_dense_bwd_s": (_I, [C.POINTER(DenseBwdT), _PI, _P]),
-    "raae_stat_collapse2": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P]),
     "raae_style_bn_fwd": (_I, [_P, _I, _I, _PB, _P, _P]),
     "raae_style_bn_bwd": (_I, [_P, _P, _I, _I, _PB, _F, _P, _P]),
     "raae_rank_loss_work_bytes": (_L, [_I, _I]),
@@ -244,7 +243,6 @@ SIGNATURES = {
     "raae_multi_free": (_I, [_P]),
     "raae_record_refusal": (_I, [C.c_char_p, _I]),
     "raae_tile_hint": (_I, [_I]),
-    "raae_tail_prepare": (_I, [_P, _P, _L, _P, _P, _P, _P]),
     "raae_graph_begin": (_I, [_P]),
     "raae_graph_end": (_I, [_P, C.POINTER(C.c_void_p)]),
     "raae_graph_launch": (_I, [_P, _P]),
