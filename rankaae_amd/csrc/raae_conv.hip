@@ -818,6 +818,12 @@ static int blk_kind_b(int Cin, int Cout, int L1, int Lout, const raae_conv_t& cv
     return -1;
 }
 
+// The strip paths of a shape instance (raae_block_fused.inc: kStrip1, kStrip2, kStripB, kStripA) move whole 16-byte
+// quads of global memory without an alignment test of their own.  A launch whose tensors do not all start on a
+// 16-byte boundary takes the generic instance instead, whose quad paths all test.  (Every caller in the package
+// passes aligned tensors: torch allocations and tape slots rounded to 4 floats.)
+static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 static int prep_block_fwd_a(const raae_block_fwd_a_t* in, raae_block_fwd_a_t& a, int& grid, size_t& lds, int& kind) {
     RAAE_CHECK_ARG(in && in->B > 0 && in->Cin >= 1 && in->Cin <= CT_MAXCH && in->Cout >= 1 && in->Cout <= CT_MAXCH);
     RAAE_CHECK_ARG(view_ok(&in->in, in->Cin) && !in->in.mask && conv_ok(&in->cv1) && (!in->has_short || conv_ok(&in->cvs)));
@@ -839,6 +845,7 @@ static int prep_block_fwd_a(const raae_block_fwd_a_t* in, raae_block_fwd_a_t& a,
     lds = sizeof(float) * ((size_t)a.S * per + conv_nw(&a.cv1) + (a.has_short ? conv_nw(&a.cvs) : 0) +
                                         (size_t)a.E * a.Lin + (size_t)a.Lout * a.E);
     kind = blk_kind_a(a.Cin, a.Cout, a.Lin, a.L1, a.Lout, a.E, a.cv1, a.has_short, a.cvs, 0, false);
+    if (kind >= 0 && strip_conv_ok(kBlk[kind].cv1) && !al16(a.T1)) kind = -1;
     return 0;
 }
 
@@ -871,6 +878,8 @@ static int prep_block_fwd_b(const raae_block_fwd_b_t* in, raae_block_fwd_b_t& a,
     grid = a.ngroups < RAAE_MAX_PARTS ? a.ngroups : RAAE_MAX_PARTS;
     lds = sizeof(float) * ((size_t)a.S * per + conv_nw(&a.cv2) + (a.has_excit ? conv_nw(&a.cve) : 0));
     kind = blk_kind_b(a.Cin, a.Cout, a.L1, a.Lout, a.cv2, a.has_short, a.has_excit, a.cve);
+    if (kind >= 0 && strip_conv_ok(kBlk[kind].cv2) && !kBlk[kind].has_excit &&
+        !(al16(a.T2) && al16(a.Y) && al16(a.vE2.raw) && al16(a.has_short ? a.Sh : a.vR.raw))) kind = -1;
     return 0;
 }
 
@@ -1010,6 +1019,7 @@ static int prep_block_bwd_b(const raae_block_bwd_b_t* in, raae_block_bwd_b_t& a,
     RAAE_CHECK_ARG(!in->has_short || (in->Sh && in->ss && in->dslope_s));
     a = *in;
     kind = blk_kind_b(a.Cin, a.Cout, a.L1, a.Lout, a.cv2, a.has_short, a.has_excit, a.cve);
+    if (kind >= 0 && strip_conv_ok(kBlk[kind].cv2) && !(al16(a.vT1.raw) && al16(a.dBn2))) kind = -1;
     // strip instances (block_bwd_b_body: kStripB) keep an 8-float zero margin on both sides of every dT2 row
     const int gm = (kind >= 0 && strip_conv_ok(kBlk[kind].cv2)) ? kStripMargin : 0;
     const long per = (long)a.Cout * (a.Lout + 2 * gm) + (a.has_excit ? (long)a.Cout * a.Lout : 0);
@@ -1047,6 +1057,8 @@ static int prep_block_bwd_a(const raae_block_bwd_a_t* in, raae_block_bwd_a_t& a,
     RAAE_CHECK_ARG(!in->pdR || (in->dR && in->in.has_bn));
     a = *in;
     kind = blk_kind_a(a.Cin, a.Cout, a.Lin, a.L1, a.Lout, a.E, a.cv1, a.has_short, a.cvs, a.has_excit, true);
+    if (kind >= 0 && strip_conv_ok(kBlk[kind].cv1) && !kBlk[kind].has_short &&
+        !(al16(a.mask) && al16(a.in.raw) && al16(a.dR))) kind = -1;
     // strip instances (block_bwd_a_kernel: kStripA) keep an 8-float zero margin on both sides of every dT1 row
     const int gm = (kind >= 0 && strip_conv_ok(kBlk[kind].cv1) && !kBlk[kind].has_short) ? kStripMargin : 0;
     const long wfl = conv_nw(&a.cv1) + (a.has_short ? conv_nw(&a.cvs) : 0) + (long)a.E * a.Lin + (long)a.Lout * a.E;
