@@ -485,14 +485,21 @@ int raae_block_bwd_b_wgrad(const raae_block_bwd_b_t* b, const raae_block_wgrad_t
  *   RAAE_CO_FWD_A  raae_block_fwd_a_t        RAAE_CO_FWD_B  raae_block_fwd_b_t        RAAE_CO_BWD_A  raae_block_bwd_a_t
  *   RAAE_CO_BWD_B_WGRAD  raae_co_bwd_b_wgrad_t (raae_block_bwd_b_wgrad's arguments)
  *   RAAE_CO_ADAM         raae_co_adam_t (raae_adam_step's arguments; nan_step != NULL: raae_optim_step_chk's)
- * *nparts_*: what the body's own entry point returns in *nparts (nothing for RAAE_CO_ADAM).  One launch for the
- * pairs of the 256-point networks' block shapes below 1024 rows (backward of decoder block i with the update or with
- * the forward of encoder block 6 - i ... ); any other pair runs as the two launches of the bodies' own entry points, x first. */
+ *   RAAE_CO_WGRAD        raae_co_wgrad_t (raae_block_wgrad's arguments: the weight-gradient tasks that end a backward pass)
+ *   RAAE_CO_HEAD_FWD     raae_co_conv_fwd_t (raae_conv_fwd's arguments; the decoder's head, as body y only)
+ * *nparts_*: what the body's own entry point returns in *nparts (nothing for RAAE_CO_ADAM and RAAE_CO_WGRAD).  One launch
+ * for the pairs of the 256-point networks' block shapes below 1024 rows (backward of decoder block i with the update or
+ * with the forward of encoder block 6 - i; since ABI 23 the encoder's backward, its last weight-gradient tasks and the
+ * update that follows with the forward of decoder blocks 0..2, and the encoder's second forward block with the decoder's
+ * head); any other pair runs as the two launches of the bodies' own entry points, x first.  raae_co_instance: 1 if the
+ * pair would be ONE launch, 0 if two, negative on an argument error; launches nothing. */
 #define RAAE_CO_FWD_A 0
 #define RAAE_CO_FWD_B 1
 #define RAAE_CO_BWD_A 2
 #define RAAE_CO_BWD_B_WGRAD 3
 #define RAAE_CO_ADAM 4
+#define RAAE_CO_WGRAD 5
+#define RAAE_CO_HEAD_FWD 6
 typedef struct { const raae_block_bwd_b_t* b; const raae_block_wgrad_t* w; int* nslab; } raae_co_bwd_b_wgrad_t;
 typedef struct {
     float *p, *m, *v; const float* g_slabs; long slab_stride; const unsigned short* seg_nslab; long n;
@@ -500,8 +507,13 @@ typedef struct {
     const double* hyper; const int* step; int max_nslab;
     int* nan_step;             /* NULL: unchecked */
 } raae_co_adam_t;
+typedef struct { const raae_block_wgrad_t* w; int* nslab; } raae_co_wgrad_t;
+typedef struct {
+    const raae_view_t* in; int B; const raae_conv_t* cv; const float* w; const float* bias; float* out; int act;
+} raae_co_conv_fwd_t;      /* raae_conv_fwd with stats_kind RAAE_OUT_RAW */
 int raae_co_launch(int kind_x, const void* args_x, int kind_y, const void* args_y, int* nparts_x, int* nparts_y,
                    void* stream);
+int raae_co_instance(int kind_x, const void* args_x, int kind_y, const void* args_y);
 
 /* Data parallel (replaces the reference's ipyparallel trial farm, sc/cmd/train_sc.py:25-45, per the
  * north star): out[i] = fixed-order sum of the slabs of element i -- the flat gradient that is then
@@ -587,7 +599,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 22
+#define RAAE_ABI_VERSION 23
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

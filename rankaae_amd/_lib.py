@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librankaae_hip.so")
 
 RAAE_MAX_PARTS = 512
-ABI_VERSION = 22
+ABI_VERSION = 23
 IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP = 0, 1, 2
 OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS, OUT_RELU = 0, 1, 2, 3, 4
 G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU = 0, 1, 2, 3, 4
@@ -151,7 +151,8 @@ class BlockWgradT(C.Structure):
                 ("conv", WgradConvT * 4), ("lin", WgradLinT * 2)]
 
 
-CO_FWD_A, CO_FWD_B, CO_BWD_A, CO_BWD_B_WGRAD, CO_ADAM = 0, 1, 2, 3, 4      # RAAE_CO_*: body kinds of raae_co_launch
+# RAAE_CO_*: body kinds of raae_co_launch
+CO_FWD_A, CO_FWD_B, CO_BWD_A, CO_BWD_B_WGRAD, CO_ADAM, CO_WGRAD, CO_HEAD_FWD = 0, 1, 2, 3, 4, 5, 6
 
 
 class CoBwdBWgradT(C.Structure):
@@ -164,6 +165,17 @@ class CoAdamT(C.Structure):
     _fields_ = [("p", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("g_slabs", C.c_void_p),
                 ("slab_stride", C.c_long), ("seg_nslab", C.c_void_p), ("n", C.c_long), ("rule", C.c_int),
                 ("hyper", C.c_void_p), ("step", C.c_void_p), ("max_nslab", C.c_int), ("nan_step", C.c_void_p)]
+
+
+class CoWgradT(C.Structure):
+    """``raae_co_wgrad_t``"""
+    _fields_ = [("w", C.POINTER(BlockWgradT)), ("nslab", C.POINTER(C.c_int))]
+
+
+class CoConvFwdT(C.Structure):
+    """``raae_co_conv_fwd_t``"""
+    _fields_ = [("inp", C.POINTER(ViewT)), ("B", C.c_int), ("cv", C.POINTER(ConvT)), ("w", C.c_void_p),
+                ("bias", C.c_void_p), ("out", C.c_void_p), ("act", C.c_int)]
 
 
 class HipLibraryMissing(RuntimeError):
@@ -230,6 +242,7 @@ SIGNATURES = {
     "raae_block_wgrad": (_I, [C.POINTER(BlockWgradT), _PI, _P]),
     "raae_block_bwd_b_wgrad": (_I, [C.POINTER(BlockBwdBT), C.POINTER(BlockWgradT), _PI, _PI, _P]),
     "raae_co_launch": (_I, [_I, _P, _I, _P, _PI, _PI, _P]),
+    "raae_co_instance": (_I, [_I, _P, _I, _P]),
     "raae_slab_reduce": (_I, [_P, _L, _P, _L, _P, _I, _P]),
     "raae_step_tick": (_I, [_P, _I, C.c_uint, _P, _P, _I, _P]),
     "raae_step_begin": (_I, [C.POINTER(StepBeginT), _P]),

@@ -956,8 +956,11 @@ __global__ __launch_bounds__(256) void block_fwd_b2_kernel_m(const FwdB2Args* ta
     }
 }
 
-// instances: encoder block i beside decoder block i of the 256-point networks; anything else: two launches
+// instances: encoder block i beside decoder block i of the 256-point networks, and encoder block 0 beside the decoder's
+// last block (a decoder forward that began in the launches of the phase before: StepEngine.emit_step); anything else:
+// two launches
 #define RAAE_FWD_PAIRS(KERNEL) \
+    if (k1 == 0 && k2 == 6) { raae::launch(KERNEL<0, 6>, KERNEL##_m<0, 6>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); } \
     if (k1 == 0 && k2 == 3) { raae::launch(KERNEL<0, 3>, KERNEL##_m<0, 3>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); } \
     if (k1 == 1 && k2 == 4) { raae::launch(KERNEL<1, 4>, KERNEL##_m<1, 4>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); } \
     if (k1 == 2 && k2 == 5) { raae::launch(KERNEL<2, 5>, KERNEL##_m<2, 5>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); }
@@ -1274,6 +1277,14 @@ template <bool CHK> struct CoAdam {             // adam_wide_kernel / adam_wide_
                             c.nan_step, bx, gx);
     }
 };
+template <int KW> struct CoWgrad {               // wgrad_multi_kernel<KW>: the weight-gradient tasks that end a backward pass
+    typedef WgradMultiArgs Args;
+    static __device__ __forceinline__ void body(const Args& m, int bx, int, float* dyn) { wgrad_multi_body<KW>(m, bx, dyn); }
+};
+template <int C> struct CoHeadFwd {              // head_fwd_kernel<C> (raae_head.inc)
+    typedef HeadFwdArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float*) { head_fwd_body<C>(a, bx, gx); }
+};
 template <class X, class Y> struct CoArgs { typename X::Args x; typename Y::Args y; int n1; };
 template <class X, class Y>
 __global__ __launch_bounds__(256) void co_kernel(CoArgs<X, Y> k) {
@@ -1319,7 +1330,8 @@ struct CoSide {
     size_t lds = 0;
     bool big = false, chk = false, wide = false;
     int max_nslab = 0;
-    BlockFwdAArgs fa; BlockFwdBArgs fb; BlockBwdAArgs ba; BwdBWgradArgs bw; AdamChkArgs ad;
+    BlockFwdAArgs fa; BlockFwdBArgs fb; BlockBwdAArgs ba; BwdBWgradArgs bw; AdamChkArgs ad; WgradMultiArgs wg; HeadFwdArgs hf;
+    raae_co_conv_fwd_t cf;
 };
 static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
     RAAE_CHECK_ARG(args);
@@ -1370,6 +1382,30 @@ static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
         s.grid = (int)g; s.lds = 0;
         return 0;
     }
+    case RAAE_CO_WGRAD: {
+        const raae_co_wgrad_t* p = (const raae_co_wgrad_t*)args;
+        RAAE_CHECK_ARG(p->w && p->nslab);
+        rc = prep_block_wgrad(p->w, p->nslab, s.wg, s.grid, s.lds, s.k);
+        if (rc) return rc;
+        s.big = use_big(p->w->B, s.k, kFamWgrad);
+        return 0;                               // (nothing in *nparts: the slab counts are in p->nslab)
+    }
+    case RAAE_CO_HEAD_FWD: {
+        const raae_co_conv_fwd_t* p = (const raae_co_conv_fwd_t*)args;
+        RAAE_CHECK_ARG(p->in && p->cv && conv_ok(p->cv) && view_ok(p->in, p->cv->Cin) && p->w && p->bias && p->out && p->B > 0);
+        s.cf = *p;
+        s.k = -1; s.grid = 0; s.lds = 0; s.big = false;
+        if (head_shape_ok(p->cv, p->in) && (reinterpret_cast<uintptr_t>(p->out) & 15) == 0) {     // as raae_conv_fwd
+            HeadFwdArgs& h = s.hf;
+            h.in = *p->in; h.B = p->B; h.L = p->cv->Lin; h.w = p->w; h.bias = p->bias; h.out = p->out; h.act = p->act;
+            h.nq = p->B * (p->cv->Lin >> 2);
+            s.k = p->cv->Cin;
+            s.grid = head_grid(h.nq, p->cv->Cin <= 4 ? kHeadU : kHeadU / 2);
+            s.big = p->B >= RAAE_BIG_ROWS;
+        }
+        if (nparts) *nparts = 0;
+        return 0;
+    }
     default:
         return RAAE_EINVAL;
     }
@@ -1385,6 +1421,10 @@ static int co_single(const CoSide& s, hipStream_t stream) {
     case RAAE_CO_FWD_B: { const raae_block_fwd_b_t& a = s.fb; RAAE_LAUNCH_KIND_BIG(block_fwd_b_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
     case RAAE_CO_BWD_A: { const raae_block_bwd_a_t& a = s.ba; RAAE_LAUNCH_KIND_BIG(block_bwd_a_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
     case RAAE_CO_BWD_B_WGRAD: return launch_bwd_b_wgrad(s.bw, s.k, s.kw, dim3(s.grid), s.lds, stream);
+    case RAAE_CO_WGRAD: { const WgradMultiArgs& m = s.wg; RAAE_LAUNCH_KIND_BIG(wgrad_multi_kernel, dim3(s.grid), dim3(256), s.lds, stream, m) break; }
+    case RAAE_CO_HEAD_FWD:
+        return raae_conv_fwd(s.cf.in, s.cf.B, s.cf.cv, s.cf.w, s.cf.bias, s.cf.out, RAAE_OUT_RAW, nullptr, nullptr, nullptr,
+                             s.cf.act, stream);
     default: {
         const AdamArgs& a = s.ad.a;
         if (s.chk) return raae_optim_step_chk(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n,
@@ -1397,32 +1437,59 @@ static int co_single(const CoSide& s, hipStream_t stream) {
     RAAE_LAUNCH_RET();
 }
 
+// the pair as ONE launch if it has an instance (`dry`: only say whether it has): 1, else 0
+static int co_pair(const CoSide& x, const CoSide& y, hipStream_t st, bool dry) {
+    const size_t lds = x.lds > y.lds ? x.lds : y.lds;
+    if (x.big || y.big) return 0;
+    // instances, 256-point networks.  The decoder backward (blocks 6, 5, 4, 3) carrying the encoder's Adam half and then
+    // the encoder forward (blocks 0, 1, 2); the encoder backward (blocks 2, 1, 0), its last weight-gradient tasks and the
+    // update behind it carrying the decoder's Adam half and then the decoder forward's blocks 3, 4, 5; the encoder
+    // forward's second block carrying the decoder's head.  Anything else: two launches.
+#define RAAE_CO(XK, XCOND, XT, XF, YK, YCOND, YT, YF) if (x.kind == XK && (XCOND) && y.kind == YK && (YCOND)) { \
+        if (!dry) co_go<XT, YT>(x.XF, y.YF, x.grid, y.grid, lds, st); return 1; }
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
+    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 5 && x.kw == 6, CoBwdBW<5 COMMA 6>, bw, RAAE_CO_FWD_A, y.k == 0, CoFwdA<0>, fa)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 5, CoBwdA<5>, ba, RAAE_CO_FWD_B, y.k == 0, CoFwdB<0>, fb)
+    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 4 && x.kw == 5, CoBwdBW<4 COMMA 5>, bw, RAAE_CO_FWD_A, y.k == 1, CoFwdA<1>, fa)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 4, CoBwdA<4>, ba, RAAE_CO_FWD_B, y.k == 1, CoFwdB<1>, fb)
+    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 3 && x.kw == 4, CoBwdBW<3 COMMA 4>, bw, RAAE_CO_FWD_A, y.k == 2, CoFwdA<2>, fa)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 3, CoBwdA<3>, ba, RAAE_CO_FWD_B, y.k == 2, CoFwdB<2>, fb)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 2, CoBwdA<2>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 2, CoBwdA<2>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
+    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 1 && x.kw == 2, CoBwdBW<1 COMMA 2>, bw, RAAE_CO_FWD_A, y.k == 3, CoFwdA<3>, fa)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 1, CoBwdA<1>, ba, RAAE_CO_FWD_B, y.k == 3, CoFwdB<3>, fb)
+    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 0 && x.kw == 1, CoBwdBW<0 COMMA 1>, bw, RAAE_CO_FWD_A, y.k == 4, CoFwdA<4>, fa)
+    RAAE_CO(RAAE_CO_BWD_A, x.k == 0, CoBwdA<0>, ba, RAAE_CO_FWD_B, y.k == 4, CoFwdB<4>, fb)
+    RAAE_CO(RAAE_CO_WGRAD, x.k == 0, CoWgrad<0>, wg, RAAE_CO_FWD_A, y.k == 5, CoFwdA<5>, fa)
+    RAAE_CO(RAAE_CO_ADAM, x.wide && x.chk, CoAdam<true>, ad, RAAE_CO_FWD_B, y.k == 5, CoFwdB<5>, fb)
+    RAAE_CO(RAAE_CO_ADAM, x.wide && !x.chk, CoAdam<false>, ad, RAAE_CO_FWD_B, y.k == 5, CoFwdB<5>, fb)
+    RAAE_CO(RAAE_CO_FWD_A, x.k == 1, CoFwdA<1>, fa, RAAE_CO_HEAD_FWD, y.k == 4, CoHeadFwd<4>, hf)
+#undef RAAE_CO
+    return 0;
+}
+
 extern "C" int raae_co_launch(int kind_x, const void* args_x, int kind_y, const void* args_y, int* nparts_x,
                               int* nparts_y, void* stream) {
     static thread_local CoSide x, y;
+    RAAE_CHECK_ARG(kind_x != RAAE_CO_HEAD_FWD);
     int rc = co_prep(kind_x, args_x, nparts_x, x);
     if (rc) return rc;
     rc = co_prep(kind_y, args_y, nparts_y, y);
     if (rc) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    const size_t lds = x.lds > y.lds ? x.lds : y.lds;
-    if (!x.big && !y.big) {
-        // instances: what the decoder backward of the 256-point networks (blocks 6, 5, 4, 3) meets when the encoder's
-        // Adam half and then the encoder forward (blocks 0, 1, 2) ride in it; anything else: two launches
-#define RAAE_CO(XK, XCOND, XT, XF, YK, YCOND, YT, YF) if (x.kind == XK && (XCOND) && y.kind == YK && (YCOND)) { \
-            co_go<XT, YT>(x.XF, y.YF, x.grid, y.grid, lds, st); RAAE_LAUNCH_RET(); }
-        RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
-        RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
-        RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 5 && x.kw == 6, CoBwdBW<5 COMMA 6>, bw, RAAE_CO_FWD_A, y.k == 0, CoFwdA<0>, fa)
-        RAAE_CO(RAAE_CO_BWD_A, x.k == 5, CoBwdA<5>, ba, RAAE_CO_FWD_B, y.k == 0, CoFwdB<0>, fb)
-        RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 4 && x.kw == 5, CoBwdBW<4 COMMA 5>, bw, RAAE_CO_FWD_A, y.k == 1, CoFwdA<1>, fa)
-        RAAE_CO(RAAE_CO_BWD_A, x.k == 4, CoBwdA<4>, ba, RAAE_CO_FWD_B, y.k == 1, CoFwdB<1>, fb)
-        RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 3 && x.kw == 4, CoBwdBW<3 COMMA 4>, bw, RAAE_CO_FWD_A, y.k == 2, CoFwdA<2>, fa)
-        RAAE_CO(RAAE_CO_BWD_A, x.k == 3, CoBwdA<3>, ba, RAAE_CO_FWD_B, y.k == 2, CoFwdB<2>, fb)
-#undef RAAE_CO
-    }
+    if (co_pair(x, y, st, false)) RAAE_LAUNCH_RET();
     rc = co_single(x, st);
     if (rc) return rc;
     return co_single(y, st);
+}
+
+extern "C" int raae_co_instance(int kind_x, const void* args_x, int kind_y, const void* args_y) {
+    static thread_local CoSide x, y;
+    int rc = co_prep(kind_x, args_x, nullptr, x);
+    if (rc) return rc < 0 ? rc : -rc;
+    rc = co_prep(kind_y, args_y, nullptr, y);
+    if (rc) return rc < 0 ? rc : -rc;
+    return co_pair(x, y, nullptr, true);
 }
 #undef COMMA

@@ -18,18 +18,19 @@ struct HeadBwdArgs {
 
 constexpr int kHeadU = 4;          // quads per thread and trip of the forward kernel (all loads of a trip in flight together)
 
+// `bx` / `gx`: the workgroup's index and the number of workgroups among those that run this body (co_kernel)
 template <int C>
-__device__ __forceinline__ void head_fwd_body(const HeadFwdArgs& a) {
+__device__ __forceinline__ void head_fwd_body(const HeadFwdArgs& a, const int bx, const int gx) {
     __shared__ ViewStats vs;
-    view_prologue(a.in, C, &vs, blockIdx.x == 0);
+    view_prologue(a.in, C, &vs, bx == 0);
     float wc[C], mu[C], rs[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) { wc[c] = a.w[c]; mu[c] = vs.mean[c]; rs[c] = vs.rstd[c]; }
     const float bias = a.bias[0];
     const int L4 = a.L >> 2;
-    const int stride = gridDim.x * 256;
+    const int stride = gx * 256;
     constexpr int U = C <= 4 ? kHeadU : kHeadU / 2;
-    for (int q0 = blockIdx.x * 256 + threadIdx.x; q0 < a.nq; q0 += U * stride) {
+    for (int q0 = bx * 256 + threadIdx.x; q0 < a.nq; q0 += U * stride) {
         float4 x[U][C];
         size_t oi[U];
         bool ok[U];
@@ -68,11 +69,11 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwdArgs& a) {
 }
 
 template <int C>
-__global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) { head_fwd_body<C>(a); }
+__global__ __launch_bounds__(256) void head_fwd_kernel(HeadFwdArgs a) { head_fwd_body<C>(a, blockIdx.x, gridDim.x); }
 template <int C>
 __global__ __launch_bounds__(256) void head_fwd_kernel_m(const HeadFwdArgs* t) {      // one trial per grid plane
     const HeadFwdArgs a = t[blockIdx.z];
-    head_fwd_body<C>(a);
+    head_fwd_body<C>(a, blockIdx.x, gridDim.x);
 }
 
 template <int C>

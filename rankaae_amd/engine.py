@@ -876,15 +876,19 @@ class StepEngine:
         return P
 
     # -- emit the step program (eagerly or under capture)
-    def _adam(self, P, name, notes_host, part=None, ride=False):
+    def _adam(self, P, name, notes_host, part=None, ride=False, first=None):
         """The update of optimizer ``name``.  ``part`` ("enc" / "dec"): only that network's slice of the optimizer's
-        range (the rules are element-wise, the step count is advanced by the step's head, and both halves get the whole
-        range's slab hint, so the two halves together are bit for bit the one launch); ``ride``: do not launch, return
-        the ``("adam", launch)`` item for ``CompactNet.lockstep``."""
+        range (the rules are element-wise, the step count is advanced by the step's head, and both halves choose the
+        kernel the whole range's slab hint chooses, so the two halves together are bit for bit the one launch); ``first``:
+        this half runs before the other network's gradients are complete (default: the encoder's half does); ``ride``: do
+        not launch, return the ``("adam", launch)`` item for ``CompactNet.lockstep``."""
         o = self.opts[name]
+        if first is None:
+            first = part == "enc"
+        assert part is not None or not first
         if notes_host is not None:
             P.seg[name].copy_(torch.from_numpy(notes_host))
-            if part is None or part == "dec":     # (a first half sees only its own network's counts: _cross_ready)
+            if not first:       # (a first half sees only its own network's counts: `cross_ok` in emit_step)
                 P.max_slab[name] = int(notes_host.max())      # host-side hint for the Adam kernel's lane split
         self.join_side_streams()
         if self.phase_hook is not None:      # debugging / parity tests: gradients before the update
@@ -903,7 +907,7 @@ class StepEngine:
             g, seg, max_slab = self.G_flat[lo:], self.seg_ones[lo // 64:], 1
         else:
             g, seg, max_slab = self.G[0, lo:], P.seg[name][lo // 64:], P.max_slab[name]
-        if part is not None and notes_host is not None and part != "dec":
+        if first and notes_host is not None:
             max_slab = max(max_slab, int(notes_host[lo // 64:(lo + n) // 64].max()))
         nan = self.nan_flags[o.index:o.index + 1] if self.detect_anomaly else None
 
@@ -926,6 +930,18 @@ class StepEngine:
         launch()
         if self.post_phase_hook is not None:  # parity tests: teacher forcing at phase granularity
             self._host_hook(self.post_phase_hook, name, P)
+
+    @staticmethod
+    def _then(steps, last, first=None):
+        """A generator of launches (``backward_steps``; ``first``: the item it has already yielded) followed by one more
+        item, ``last()`` -- evaluated when its turn comes, i.e. after everything ``steps`` has recorded."""
+        try:
+            item = next(steps) if first is None else first
+            while True:
+                item = steps.send((yield item))
+        except StopIteration:
+            pass
+        yield last()
 
     def _host_hook(self, fn, name, P):
         """A host callback between two launches (parity tests).  Eager emission: call it now.  Under capture: the
@@ -1046,19 +1062,44 @@ class StepEngine:
         # issued first: true for the dense networks and for fused residual blocks, not for the per-layer conv path.
         pair = ((not self._branch) and bool(c.get("pair_unused_forwards", True)) and
                 getattr(enc, "pairable", False) and getattr(dec, "pairable", False))
+        # Across the phase boundaries (build-only key `pair_across_phases`: True, the default, = all of "AB", "CD", "DE";
+        # a list names the boundaries to cross; False: none.  Serial chain of the fused conv networks only): where a phase
+        # ends in launches that touch one network and the next begins with a forward pass that reads only the other
+        # (and the tape), that forward's launches ride in the ending phase's (CompactNet.lockstep).  Same kernels' bodies
+        # on the same operands: bit for bit the serial order (tests/test_cross_phase_gpu.py, test_cross_phase_ab_cd_gpu.py).
+        across = c.get("pair_across_phases", True)
+        across = set(across) if isinstance(across, (list, tuple, set)) else ({"AB", "CD", "DE"} if across else set())
+        assert across <= {"AB", "CD", "DE"}, across
+        crossable = (pair and self.world_size == 1 and self.phase_hook is None and self.post_phase_hook is None and
+                     hasattr(enc, "backward_steps") and hasattr(dec, "backward_steps"))
         if not pair:
             with self.aux_branch():
                 dec.forward(D, styles, P.m_dec[0])
         # ---- phase A: adversarial (trainer.py:117-127)
         self._begin_phase(record)
         dst = self.disc.forward_backward(P.disc, P.sl_disc, styles, lo[0:1])
-        enc.backward(E, P.spec, P.m_enc[0], dst)
-        self.join_aux()
-        self._adam(P, "adversarial", self._slab_notes)
+        dec_fwd = None
+        if crossable and "AB" in across:
+            # A/B: the deferred decoder forward reads `styles` and decoder state; the encoder backward and this phase's
+            # update (discriminator and encoder) touch neither.  Its block kernels ride in the encoder backward's
+            # launches, in the weight-gradient tasks that end it and in the update; what is left of it pairs with phase
+            # B's encoder forward below.
+            steps = enc.backward_steps(E, P.spec, P.m_enc[0], dst)
+            _, dec_fwd = enc.lockstep(self._then(steps, lambda: self._adam(P, "adversarial", self._slab_notes, ride=True)),
+                                      dec.forward_steps(D, styles, P.m_dec[0]), finish_rider=False)
+        else:
+            enc.backward(E, P.spec, P.m_enc[0], dst)
+            self.join_aux()
+            self._adam(P, "adversarial", self._slab_notes)
         # ---- phase B: rank correlation (:153-161)
         self._begin_phase(record)
         if pair:
-            styles, _ = enc.forward_pair(enc.forward_steps(E, P.spec, P.m_enc[1]), dec.forward_steps(D, styles, P.m_dec[0]))
+            if dec_fwd is None:
+                dec_fwd = dec.forward_steps(D, styles, P.m_dec[0])
+            if not (isinstance(dec_fwd, tuple) and dec_fwd[0] is None):     # (else: it has ended beside phase A)
+                styles, _ = enc.forward_pair(enc.forward_steps(E, P.spec, P.m_enc[1]), dec_fwd)
+            else:
+                styles = enc.forward(E, P.spec, P.m_enc[1])
         else:
             styles = enc.forward(E, P.spec, P.m_enc[1])
         self._rank_loss(P, styles)
@@ -1071,15 +1112,47 @@ class StepEngine:
         ops.recon_loss_fwd_bwd(P.spec, out, b, self.L, c["use_flex_spec_target"], P.lpart, P.dout,
                                fin=(1.0, lo, 2, -1, P.ticket))
         left = dec.backward(D, styles, P.m_dec[1], P.dout, P.dstyles, keep_pending=True)
-        enc.backward(E, P.spec, P.m_enc[2], P.dstyles, pending=left)
-        self._adam(P, "reconstruction", self._slab_notes)
+        z_s = tape.view(P.z_sample, b, ns)
+        dec_fwd = None
+        if crossable and "CD" in across and left is not None:
+            # C/D: phase D's decoder forward reads the tape (z_sample, masks) and decoder state.  The decoder's gradients
+            # are complete once the encoder's first block launch has carried decoder block 0's weight-gradient tasks, and
+            # the decoder's workspace is dead from there: the decoder's half of this phase's update and then the decoder
+            # forward ride in the rest of the encoder backward and in the encoder's half of the update (the D/E
+            # construction below with the networks swapped).
+            steps = enc.backward_steps(E, P.spec, P.m_enc[2], P.dstyles, pending=left)
+            first = next(steps)                  # (style_bn_bwd and dense_bwd have been launched inline)
+            first = steps.send(ops.launch_item(first[0], first[1]))      # block_bwd_b_wgrad: the decoder's gradients are complete
+            # Both halves must choose the kernel one launch over the range would (see D/E): more than 16 slabs somewhere
+            # in the DECODER's slice already
+            if record:
+                r0, r1 = self.arena.ranges["dec"]
+                P.cross_ok_cd = int(self._slab_notes[r0 // 64:r1 // 64].max()) > 16
+            if getattr(P, "cross_ok_cd", False):
+                def rider_cd():
+                    yield self._adam(P, "reconstruction", self._slab_notes, part="dec", ride=True, first=True)
+                    return (yield from dec.forward_steps(D, z_s, P.m_dec[2]))
+                host = self._then(steps, lambda: self._adam(P, "reconstruction", self._slab_notes, part="enc", ride=True,
+                                                            first=False), first)
+                _, dec_fwd = enc.lockstep(host, rider_cd(), finish_rider=False)
+            else:
+                enc.drive(steps, first)
+                self._adam(P, "reconstruction", self._slab_notes)
+        else:
+            enc.backward(E, P.spec, P.m_enc[2], P.dstyles, pending=left)
+            self._adam(P, "reconstruction", self._slab_notes)
         # ---- phase D: mutual information (:175-186)
         self._begin_phase(record)
-        z_s = tape.view(P.z_sample, b, ns)
         if pair:
             # the encoder forward whose result the reference does not use (BN stats + RNG only) and the decoder
             # forward, which only needs z_sample, in lockstep: one launch per pair of block kernels
-            _, out = enc.forward_pair(enc.forward_steps(E, P.spec, P.m_enc[3]), dec.forward_steps(D, z_s, P.m_dec[2]))
+            if dec_fwd is None:
+                dec_fwd = dec.forward_steps(D, z_s, P.m_dec[2])
+            if not (isinstance(dec_fwd, tuple) and dec_fwd[0] is None):
+                _, out = enc.forward_pair(enc.forward_steps(E, P.spec, P.m_enc[3]), dec_fwd)
+            else:
+                enc.forward(E, P.spec, P.m_enc[3])
+                out = dec_fwd[1]
         else:
             with self.aux_branch():                 # ... or on the auxiliary stream, beside the decoder forward
                 enc.forward(E, P.spec, P.m_enc[3])
@@ -1088,15 +1161,11 @@ class StepEngine:
         z_rec = enc.forward(E, out, P.m_enc[4])
         ops.mse_fwd_bwd(z_rec, z_s, b * ns, P.lpart, P.dstyles, fin=(1.0, lo, 3, 5, P.ticket))
         left = enc.backward(E, out, P.m_enc[4], P.dstyles, P.dspec, keep_pending=True)
-        # Across the phase boundary (build-only key `pair_across_phases`, default on; serial chain of the fused conv
-        # networks only): the smoothness phase's encoder forward reads encoder state only, this phase's decoder backward
-        # decoder state only.  Once the decoder's first block launch has carried the encoder's last weight-gradient tasks,
-        # the encoder's half of this phase's update and then the encoder forward ride in the decoder backward's launches
-        # (CompactNet.lockstep); the decoder's half of the update follows.  Same kernels' bodies on the same operands:
-        # bit for bit the serial order (tests/test_cross_phase_gpu.py).
-        cross = (pair and smooth and left is not None and self.world_size == 1 and
-                 bool(c.get("pair_across_phases", True)) and self.phase_hook is None and
-                 self.post_phase_hook is None and hasattr(dec, "backward_steps"))
+        # D/E: the smoothness phase's encoder forward reads encoder state only, this phase's decoder backward decoder
+        # state only.  Once the decoder's first block launch has carried the encoder's last weight-gradient tasks, the
+        # encoder's half of this phase's update and then the encoder forward ride in the decoder backward's launches;
+        # the decoder's half of the update follows.
+        cross = crossable and "DE" in across and smooth and left is not None
         styles_e = None
         if cross:
             steps = dec.backward_steps(D, z_s, P.m_dec[2], P.dspec, None, pending=left)

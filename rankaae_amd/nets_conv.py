@@ -172,18 +172,20 @@ class CompactNet:
         try:
             kind, args, nbytes = next(steps)
             while True:
-                n = ops.block_fwd_a(args) if kind == "a" else ops.block_fwd_b(args)
-                kind, args, nbytes = steps.send(n)
+                kind, args, nbytes = steps.send(ops.launch_item(kind, args))
         except StopIteration as done:
             return done.value
 
     @staticmethod
     def forward_pair(first, second):
         """Two independent forward passes (``forward_steps`` generators, the ENCODER's first) in lockstep: while both
-        are at the same phase of a fused block the two kernels share one launch (raae_block_fwd_a2 / _b2).
-        Returns the two outputs."""
-        gens, cur, out = [first, second], [None, None], [None, None]
-        for j in (0, 1):
+        are at the same phase of a fused block the two kernels share one launch (raae_block_fwd_a2 / _b2), and the
+        decoder's head rides in an encoder block launch that has an instance for it (raae_co_launch).  ``second`` may be
+        ``(generator, item)``: a forward pass that has already begun (``lockstep(..., finish_rider=False)``) and the item
+        it is waiting at.  Returns the two outputs."""
+        started = isinstance(second, tuple)
+        gens, cur, out = [first, second[0] if started else second], [None, second[1] if started else None], [None, None]
+        for j in ((0,) if started else (0, 1)):
             try:
                 cur[j] = next(gens[j])
             except StopIteration as done:
@@ -200,14 +202,20 @@ class CompactNet:
                 advance(0, n1)
                 advance(1, n2)
                 continue
+            if (gens[0] is not None and gens[1] is not None and cur[1][0] == "head" and
+                    ops.co_pairable(cur[0][0], cur[0][1], "head", cur[1][1])):
+                n1, n2 = ops.co_launch(cur[0][0], cur[0][1], "head", cur[1][1])
+                advance(0, n1)
+                advance(1, n2)
+                continue
             j = 0 if gens[0] is not None else 1
-            kind, args, _ = cur[j]
-            advance(j, ops.block_fwd_a(args) if kind == "a" else ops.block_fwd_b(args))
+            advance(j, ops.launch_item(cur[j][0], cur[j][1]))
         return out[0], out[1]
 
     def forward_steps(self, ws, x, masks, train=True):
         """Generator form of the forward pass: yields ``(phase, args, algorithmic bytes)`` at every fused-block
-        launch and expects the launch's partial-row count back; everything else is launched inline."""
+        launch and expects the launch's partial-row count back, and ``("head", launch, 0)`` at the decoder's head when
+        the blocks are fused; everything else is launched inline."""
         b = ws.b
         X, pX, nX = x, None, 0                # block input (raw), statistics of it
         for i, (k, w) in enumerate(zip(self.blocks, ws.blk)):
@@ -264,8 +272,13 @@ class CompactNet:
             ops.style_bn_fwd(ws.zl, b, self.out_dim, self._bn(mod.bn_style, ws.pzl, ws.nzl, b, train, True), ws.styles)
         else:
             vf = ops.make_view(X, None, self._bn(self.bn_f, pX, nX, b * last.Lout, train, True))
-            ops.conv_fwd(vf, b, self.cvf, self.conv_f.weight, self.conv_f.bias, ws.spec.view(b, 1, self.out_dim),
-                         OUT_RAW, None, None, self.act)
+            if self.pairable:
+                # the head as an item: it may ride in a launch of the forward pass this one runs beside (forward_pair)
+                yield ("head", ops.conv_fwd_item(vf, b, self.cvf, self.conv_f.weight, self.conv_f.bias,
+                                                 ws.spec.view(b, 1, self.out_dim), self.act), 0)
+            else:
+                ops.conv_fwd(vf, b, self.cvf, self.conv_f.weight, self.conv_f.bias, ws.spec.view(b, 1, self.out_dim),
+                             OUT_RAW, None, None, self.act)
         if train:
             self.eng.count_bn(self.bn_modules)
         return ws.out
@@ -288,11 +301,14 @@ class CompactNet:
             return done.value
 
     @staticmethod
-    def lockstep(main, rider, first=None):
+    def lockstep(main, rider, first=None, finish_rider=True):
         """Two independent generators of launches in lockstep: while both have a launch ready that the two-body
-        launch takes (``ops.co_pairable``: ``main`` a backward pass, ``rider`` whatever may run beside it) the two share
-        one launch (raae_co_launch); a launch of ``main`` that takes no rider goes alone, and whichever generator
-        outlives the other runs the rest alone.  ``first``: the item ``main`` has already yielded.  Returns the two results."""
+        launch takes as ONE (``ops.co_pairable``: ``main`` a backward pass and what ends it, ``rider`` whatever may run
+        beside it) the two share that launch (raae_co_launch); a launch of ``main`` that takes no rider goes alone and the
+        rider waits for the next one, and whichever generator outlives the other runs the rest alone.  ``first``: the item
+        ``main`` has already yielded.  Returns the two results; with ``finish_rider=False`` it returns as soon as ``main``
+        has ended and the rider's part of the result is ``(generator, the item it waits at)`` -- what ``forward_pair``
+        takes as its second pass -- or ``(None, result)`` if it has ended too."""
         gens, cur, out = [main, rider], [first, None], [None, None]
 
         def advance(j, n, start=False):
@@ -304,6 +320,8 @@ class CompactNet:
             advance(0, None, True)
         advance(1, None, True)
         while gens[0] is not None or gens[1] is not None:
+            if gens[0] is None and not finish_rider:
+                return out[0], (gens[1], cur[1])
             if gens[0] is not None and gens[1] is not None:
                 if ops.co_pairable(cur[0][0], cur[0][1], cur[1][0], cur[1][1]):
                     n1, n2 = ops.co_launch(cur[0][0], cur[0][1], cur[1][0], cur[1][1])
@@ -314,7 +332,7 @@ class CompactNet:
             else:
                 j = 0 if gens[0] is not None else 1
             advance(j, ops.launch_item(cur[j][0], cur[j][1]))
-        return out[0], out[1]
+        return out[0], (out[1] if finish_rider else (None, out[1]))
 
     def backward_steps(self, ws, x, masks, g_out, dx_in=None, pending=None, keep_pending=False):
         """Generator form of the backward pass: yields ``(kind, argument block)`` at every launch of the fused block

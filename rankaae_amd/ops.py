@@ -804,9 +804,20 @@ def adam_part_args(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, ste
     return a
 
 
-# what a generator of launches (nets_conv.forward_steps / backward_steps, the engine's Adam halves) yields as its first
-# two items: ("a" | "b" | "bwd_a" | "bwd_b" | "wgrad" | "adam", argument block)
-_CO_KIND = {"a": _lib.CO_FWD_A, "b": _lib.CO_FWD_B, "bwd_a": _lib.CO_BWD_A, "adam": _lib.CO_ADAM}
+def conv_fwd_item(view, B, cv, w, bias, out, act):
+    """The decoder's head (``conv_fwd`` without statistics) as an item of a generator of launches: called, it launches
+    what ``conv_fwd`` launches; ``co_args`` (``raae_co_conv_fwd_t``) lets it ride in another launch (``co_launch``)."""
+    def launch():
+        return conv_fwd(view, B, cv, w, bias, out, 0, None, None, act)
+    launch.co_args = _lib.CoConvFwdT(C.pointer(view), B, C.pointer(cv), _ptr(w), _ptr(bias), _ptr(out), act)
+    launch.co_args.nbytes = conv_bytes(cv, B)
+    launch.keep = (view, cv)
+    return launch
+
+
+# what a generator of launches (nets_conv.forward_steps / backward_steps, the engine's Adam updates) yields as its first
+# two items: ("a" | "b" | "head" | "bwd_a" | "bwd_b" | "wgrad" | "adam", argument block)
+_CO_KIND = {"a": _lib.CO_FWD_A, "b": _lib.CO_FWD_B, "bwd_a": _lib.CO_BWD_A}
 
 
 def launch_item(kind, a):
@@ -821,36 +832,61 @@ def launch_item(kind, a):
         return block_bwd_b_launch(a)
     if kind == "wgrad":
         return block_wgrad(a.B, None, None, a.slab_stride, args=a)
-    if kind == "adam":
-        return a()            # (the engine's own launch: any rule, checked or not)
+    if kind in ("adam", "head"):
+        return a()            # (the engine's own launch: any rule, checked or not; the head: conv_fwd)
     raise ValueError(kind)
 
 
+def _co_side(kind, a):
+    """One side of ``raae_co_launch``: (RAAE_CO_* kind, argument block, algorithmic bytes, name, slab-count array)."""
+    if kind == "bwd_b":
+        ns = (C.c_int * 6)()
+        return (_lib.CO_BWD_B_WGRAD, _lib.CoBwdBWgradT(C.pointer(a), C.pointer(a.wgrad), C.cast(ns, C.POINTER(C.c_int))),
+                a.nbytes + a.wgrad.nbytes, "bwd_b_wgrad", ns)
+    if kind == "wgrad":
+        ns = (C.c_int * 6)()
+        return _lib.CO_WGRAD, _lib.CoWgradT(C.pointer(a), C.cast(ns, C.POINTER(C.c_int))), a.nbytes, "wgrad", ns
+    if kind == "adam":
+        return _lib.CO_ADAM, a.co_args, a.co_args.nbytes, "adam", None
+    if kind == "head":
+        return _lib.CO_HEAD_FWD, a.co_args, a.co_args.nbytes, "head", None
+    return _CO_KIND[kind], a, a.nbytes, ("fwd_" + kind if kind in ("a", "b") else kind), None
+
+
 def co_pairable(kx, ax, ky, ay):
-    """Whether ``co_launch`` takes the two yielded launches (x: a backward launch, y: the rider)."""
-    return ((kx == "bwd_a" or (kx == "bwd_b" and ax.wgrad is not None)) and
-            (ky in ("a", "b") or (ky == "adam" and getattr(ay, "co_args", None) is not None)))
+    """Whether ``co_launch`` runs the two yielded launches as ONE (x: the host, a backward launch, the weight-gradient
+    tasks or the update that end a backward pass, or an encoder forward block; y: the rider): the library has an
+    instance for the pair (``raae_co_instance``).  Without one the host goes alone and the rider waits."""
+    if not ((kx in ("bwd_a", "wgrad", "adam", "a") or (kx == "bwd_b" and ax.wgrad is not None)) and
+            ky in ("a", "b", "adam", "head")):
+        return False
+    if (kx == "adam" and getattr(ax, "co_args", None) is None) or (ky == "adam" and getattr(ay, "co_args", None) is None):
+        return False
+    cx, px, _, _, _ = _co_side(kx, ax)
+    cy, py, _, _, _ = _co_side(ky, ay)
+    rc = _lib.load().raae_co_instance(cx, C.cast(C.pointer(px), C.c_void_p), cy, C.cast(C.pointer(py), C.c_void_p))
+    if rc < 0:
+        check(rc, "raae_co_instance")
+    return rc == 1
 
 
 def co_launch(kx, ax, ky, ay):
     """Two independent launches as one (``raae_co_launch``); returns what each would have returned alone."""
-    ns = (C.c_int * 6)()
-    if kx == "bwd_b":
-        wgrad = ax.wgrad
-        px = _lib.CoBwdBWgradT(C.pointer(ax), C.pointer(wgrad), C.cast(ns, C.POINTER(C.c_int)))
-        cx, nbx, fam = _lib.CO_BWD_B_WGRAD, ax.nbytes + wgrad.nbytes, "bwd_b_wgrad"
-    else:
-        px, cx, nbx, fam = ax, _CO_KIND[kx], ax.nbytes, kx
-    py = ay.co_args if ky == "adam" else ay
+    cx, px, nbx, namex, ns = _co_side(kx, ax)
+    cy, py, nby, namey, _ = _co_side(ky, ay)
 
     def launch():
         n1, n2 = C.c_int(0), C.c_int(0)
-        check(_lib.load().raae_co_launch(cx, C.cast(C.pointer(px), C.c_void_p), _CO_KIND[ky],
-                                         C.cast(C.pointer(py), C.c_void_p), C.byref(n1), C.byref(n2), _stream()),
-              "raae_co_launch")
-        rx = (n1.value, list(ns)[:ax.wgrad.n_conv + ax.wgrad.n_lin]) if kx == "bwd_b" else n1.value
-        return rx, (None if ky == "adam" else n2.value)
-    return _probed(f"co_kernel[{fam}+{'fwd_' + ky if ky in ('a', 'b') else ky}]", nbx + py.nbytes, launch)
+        check(_lib.load().raae_co_launch(cx, C.cast(C.pointer(px), C.c_void_p), cy, C.cast(C.pointer(py), C.c_void_p),
+                                         C.byref(n1), C.byref(n2), _stream()), "raae_co_launch")
+        if kx == "bwd_b":
+            rx = (n1.value, list(ns)[:ax.wgrad.n_conv + ax.wgrad.n_lin])
+        elif kx == "wgrad":
+            rx = list(ns)[:ax.n_conv + ax.n_lin]
+        else:
+            rx = None if kx == "adam" else n1.value
+        return rx, (None if ky in ("adam", "head") else n2.value)
+    return _probed(f"co_kernel[{namex}+{namey}]", nbx + nby, launch)
 
 
 def block_wgrad_args(B, conv_tasks, lin_tasks, slab_stride):
