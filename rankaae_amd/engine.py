@@ -23,8 +23,9 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, ops
+from . import _lib, ops, schedule
 from .metrics import StyleMetrics
+from .schedule import Pass
 from .parameter import check_optimizer, detect_anomaly_on
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
@@ -258,40 +259,17 @@ class FCNet:
 
     def forward(self, ws, x, masks, train=True):
         """One forward pass, every layer its own launch."""
-        steps = self.forward_steps(ws, x, masks, train)
-        try:
-            _, args, nbytes = next(steps)
-            while True:
-                _, args, nbytes = steps.send(ops.dense_fwd_struct(args))
-        except StopIteration as done:
-            return done.value
+        return schedule.run(Pass(self.forward_steps(ws, x, masks, train)))
 
     @staticmethod
     def forward_pair(first, second):
-        """Two independent forward passes (``forward_steps`` generators) in lockstep: layer i of both in one launch
-        (raae_dense_fwd2) while both have layers left.  Returns the two outputs."""
-        gens, cur, out = [first, second], [None, None], [None, None]
-
-        def advance(j, n):
-            try:
-                cur[j] = next(gens[j]) if n is None else gens[j].send(n)
-            except StopIteration as done:
-                out[j], gens[j], cur[j] = done.value, None, None
-        advance(0, None)
-        advance(1, None)
-        while gens[0] is not None or gens[1] is not None:
-            if gens[0] is not None and gens[1] is not None:
-                n1, n2 = ops.dense_fwd_pair(cur[0][1], cur[1][1])
-                advance(0, n1)
-                advance(1, n2)
-            else:
-                j = 0 if gens[0] is not None else 1
-                advance(j, ops.dense_fwd_struct(cur[j][1]))
-        return out[0], out[1]
+        """Two independent forward passes (``schedule.Pass`` over ``forward_steps``) in lockstep: layer i of both in one
+        launch (raae_dense_fwd2) while both have layers left.  Returns the two outputs."""
+        return schedule.lockstep(first, second, schedule.share_dense)
 
     def forward_steps(self, ws, x, masks, train=True):
-        """Generator form of the forward pass: yields ``("dense", args, algorithmic bytes)`` per layer and expects
-        the launch's partial-row count back."""
+        """Generator form of the forward pass (``schedule``): yields ``("dense", args)`` per layer and expects the
+        launch's partial-row count back."""
         eng, L, b = self.eng, self.layers, ws.b
         for i, l in enumerate(L):
             last = i == len(L) - 1
@@ -314,7 +292,7 @@ class FCNet:
                 st = (_lib.ST_X if i > 1 else 0) | (_lib.ST_MASK if mask is not None else 0) | (_lib.ST_Z if 0 < i and not last else 0)
             extra = dict(gen=mk["gen"], mask_scale=mk["mask_scale"]) if (i > 0 and mk) else {}
             ws.nparts[i] = yield ("dense", ops.dense_fwd_args(xin, b, l.K, in_kind, slope, bn, mask, l.w, l.b, l.N,
-                                                               ws.z[i], out_kind, oslope, ws.part[i], storage=st, **extra), 0)
+                                                               ws.z[i], out_kind, oslope, ws.part[i], storage=st, **extra))
         if self.kind == "enc":
             ops.style_bn_fwd(ws.z[-1], b, self.out_dim, self._bn_in(ws, len(L) - 1, train, True), ws.styles)
         if train:
@@ -871,24 +849,23 @@ class StepEngine:
         P.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # arrival counter of the in-kernel loss sums
         P.seg = {n: torch.zeros(self.arena.n // 64, dtype=torch.int16, device=dev) for n in OPT_NAMES}
         P.max_slab = {n: 0 for n in OPT_NAMES}
+        P.cross_ok = {"CD": False, "DE": False}     # whether the split update of that boundary is legal (`_cross`)
         P.graphs = {}
         self.plans[b] = P
         return P
 
     # -- emit the step program (eagerly or under capture)
-    def _adam(self, P, name, notes_host, part=None, ride=False, first=None):
+    def _adam(self, P, name, notes_host, part=None, ride=False, early=False):
         """The update of optimizer ``name``.  ``part`` ("enc" / "dec"): only that network's slice of the optimizer's
         range (the rules are element-wise, the step count is advanced by the step's head, and both halves choose the
-        kernel the whole range's slab hint chooses, so the two halves together are bit for bit the one launch); ``first``:
-        this half runs before the other network's gradients are complete (default: the encoder's half does); ``ride``: do
-        not launch, return the ``("adam", launch)`` item for ``CompactNet.lockstep``."""
+        kernel the whole range's slab hint chooses, so the two halves together are bit for bit the one launch); ``early``:
+        this half runs before the other network's gradients are complete; ``ride``: do not launch, return the
+        ``("adam", launch)`` item for ``schedule.lockstep``."""
         o = self.opts[name]
-        if first is None:
-            first = part == "enc"
-        assert part is not None or not first
+        assert part is not None or not early
         if notes_host is not None:
             P.seg[name].copy_(torch.from_numpy(notes_host))
-            if not first:       # (a first half sees only its own network's counts: `cross_ok` in emit_step)
+            if not early:       # (an early half sees only its own network's counts: `_cross`)
                 P.max_slab[name] = int(notes_host.max())      # host-side hint for the Adam kernel's lane split
         self.join_side_streams()
         if self.phase_hook is not None:      # debugging / parity tests: gradients before the update
@@ -907,7 +884,7 @@ class StepEngine:
             g, seg, max_slab = self.G_flat[lo:], self.seg_ones[lo // 64:], 1
         else:
             g, seg, max_slab = self.G[0, lo:], P.seg[name][lo // 64:], P.max_slab[name]
-        if first and notes_host is not None:
+        if early and notes_host is not None:
             max_slab = max(max_slab, int(notes_host[lo // 64:(lo + n) // 64].max()))
         nan = self.nan_flags[o.index:o.index + 1] if self.detect_anomaly else None
 
@@ -930,18 +907,6 @@ class StepEngine:
         launch()
         if self.post_phase_hook is not None:  # parity tests: teacher forcing at phase granularity
             self._host_hook(self.post_phase_hook, name, P)
-
-    @staticmethod
-    def _then(steps, last, first=None):
-        """A generator of launches (``backward_steps``; ``first``: the item it has already yielded) followed by one more
-        item, ``last()`` -- evaluated when its turn comes, i.e. after everything ``steps`` has recorded."""
-        try:
-            item = next(steps) if first is None else first
-            while True:
-                item = steps.send((yield item))
-        except StopIteration:
-            pass
-        yield last()
 
     def _host_hook(self, fn, name, P):
         """A host callback between two launches (parity tests).  Eager emission: call it now.  Under capture: the
@@ -984,9 +949,6 @@ class StepEngine:
             ev2.record(self.comm_stream)
         cur.wait_event(ev2)
 
-    def _all_reduce(self, buf):
-        self._run_comm("mean", (buf,))
-
     def _collective(self, buf, kind="mean", dst=None):
         """``kind``: "mean" (gradient arenas), "sum" (float64 pair totals), "gather" (buf -> dst).  With the private
         RCCL communicator the call is a node of the graph being captured (or an eager launch on this stream).
@@ -1021,6 +983,34 @@ class StepEngine:
 
     def _begin_phase(self, record):
         self._slab_notes = np.zeros(self.arena.n // 64, dtype=np.int16) if record else None
+
+    def _cross(self, P, boundary, host, name, halves, fwd, carry):
+        """The end of a phase whose last backward pass (``host``) touches one network while the next phase begins with a
+        forward pass (``fwd``) that reads only the other: once the host's first block launch has carried the other
+        network's last weight-gradient tasks, that network's gradients are complete.  Its half of the update of optimizer
+        ``name`` (``halves[0]``) and then ``fwd`` ride in the rest of the host's launches (``schedule.share_across``); the
+        host network's half (``halves[1]``) follows.  With ``carry`` that half hosts riders too and what is left of
+        ``fwd`` stays for the caller's next ``lockstep``; without, ``fwd`` ends here.  Returns ``fwd``, or None where the
+        plan does not cross this boundary: then the host and the whole update went alone."""
+        notes = self._slab_notes
+        host.prime()             # (inline: style_bn_bwd and dense_bwd of the encoder, the head's backward of the decoder)
+        host.launch()            # block_bwd_b_wgrad: the other network's gradients are complete
+        # Both halves must choose the kernel one launch over the range would: that needs more than 16 slabs somewhere in
+        # the EARLY half's slice already (the host's counts are not all known on the first, eager emission, which decides)
+        if notes is not None:
+            r0, r1 = self.arena.ranges[halves[0]]
+            P.cross_ok[boundary] = int(notes[r0 // 64:r1 // 64].max()) > 16
+        if not P.cross_ok[boundary]:
+            schedule.run(host)
+            self._adam(P, name, notes)
+            return None
+        rider = schedule.chain(schedule.item(lambda: self._adam(P, name, notes, part=halves[0], ride=True, early=True)), fwd)
+        if carry:
+            host = schedule.chain(host, schedule.item(lambda: self._adam(P, name, notes, part=halves[1], ride=True)))
+        schedule.lockstep(host, rider, schedule.share_across, until_host_ends=carry)
+        if not carry:
+            self._adam(P, name, notes, part=halves[1])
+        return fwd
 
     def emit_step(self, P, smooth, record):
         """``record``: first (eager) emission -- slab counts are recorded into the Adam segment
@@ -1065,7 +1055,7 @@ class StepEngine:
         # Across the phase boundaries (build-only key `pair_across_phases`: True, the default, = all of "AB", "CD", "DE";
         # a list names the boundaries to cross; False: none.  Serial chain of the fused conv networks only): where a phase
         # ends in launches that touch one network and the next begins with a forward pass that reads only the other
-        # (and the tape), that forward's launches ride in the ending phase's (CompactNet.lockstep).  Same kernels' bodies
+        # (and the tape), that forward's launches ride in the ending phase's (schedule.lockstep).  Same kernels' bodies
         # on the same operands: bit for bit the serial order (tests/test_cross_phase_gpu.py, test_cross_phase_ab_cd_gpu.py).
         across = c.get("pair_across_phases", True)
         across = set(across) if isinstance(across, (list, tuple, set)) else ({"AB", "CD", "DE"} if across else set())
@@ -1084,9 +1074,10 @@ class StepEngine:
             # update (discriminator and encoder) touch neither.  Its block kernels ride in the encoder backward's
             # launches, in the weight-gradient tasks that end it and in the update; what is left of it pairs with phase
             # B's encoder forward below.
-            steps = enc.backward_steps(E, P.spec, P.m_enc[0], dst)
-            _, dec_fwd = enc.lockstep(self._then(steps, lambda: self._adam(P, "adversarial", self._slab_notes, ride=True)),
-                                      dec.forward_steps(D, styles, P.m_dec[0]), finish_rider=False)
+            dec_fwd = Pass(dec.forward_steps(D, styles, P.m_dec[0]))
+            schedule.lockstep(schedule.chain(Pass(enc.backward_steps(E, P.spec, P.m_enc[0], dst)),
+                                             schedule.item(lambda: self._adam(P, "adversarial", self._slab_notes, ride=True))),
+                              dec_fwd, schedule.share_across, until_host_ends=True)
         else:
             enc.backward(E, P.spec, P.m_enc[0], dst)
             self.join_aux()
@@ -1095,11 +1086,8 @@ class StepEngine:
         self._begin_phase(record)
         if pair:
             if dec_fwd is None:
-                dec_fwd = dec.forward_steps(D, styles, P.m_dec[0])
-            if not (isinstance(dec_fwd, tuple) and dec_fwd[0] is None):     # (else: it has ended beside phase A)
-                styles, _ = enc.forward_pair(enc.forward_steps(E, P.spec, P.m_enc[1]), dec_fwd)
-            else:
-                styles = enc.forward(E, P.spec, P.m_enc[1])
+                dec_fwd = Pass(dec.forward_steps(D, styles, P.m_dec[0]))
+            styles, _ = enc.forward_pair(Pass(enc.forward_steps(E, P.spec, P.m_enc[1])), dec_fwd)
         else:
             styles = enc.forward(E, P.spec, P.m_enc[1])
         self._rank_loss(P, styles)
@@ -1113,31 +1101,15 @@ class StepEngine:
                                fin=(1.0, lo, 2, -1, P.ticket))
         left = dec.backward(D, styles, P.m_dec[1], P.dout, P.dstyles, keep_pending=True)
         z_s = tape.view(P.z_sample, b, ns)
+        # C/D: phase D's decoder forward reads the tape (z_sample, masks) and decoder state.  The decoder's gradients are
+        # complete once the encoder's first block launch has carried decoder block 0's weight-gradient tasks, and the
+        # decoder's workspace is dead from there: the decoder's half of this phase's update and then the decoder forward
+        # ride in the rest of the encoder backward and in the encoder's half of the update (the D/E construction below
+        # with the networks swapped); what is left of the forward goes on beside phase D's encoder forward.
         dec_fwd = None
         if crossable and "CD" in across and left is not None:
-            # C/D: phase D's decoder forward reads the tape (z_sample, masks) and decoder state.  The decoder's gradients
-            # are complete once the encoder's first block launch has carried decoder block 0's weight-gradient tasks, and
-            # the decoder's workspace is dead from there: the decoder's half of this phase's update and then the decoder
-            # forward ride in the rest of the encoder backward and in the encoder's half of the update (the D/E
-            # construction below with the networks swapped).
-            steps = enc.backward_steps(E, P.spec, P.m_enc[2], P.dstyles, pending=left)
-            first = next(steps)                  # (style_bn_bwd and dense_bwd have been launched inline)
-            first = steps.send(ops.launch_item(first[0], first[1]))      # block_bwd_b_wgrad: the decoder's gradients are complete
-            # Both halves must choose the kernel one launch over the range would (see D/E): more than 16 slabs somewhere
-            # in the DECODER's slice already
-            if record:
-                r0, r1 = self.arena.ranges["dec"]
-                P.cross_ok_cd = int(self._slab_notes[r0 // 64:r1 // 64].max()) > 16
-            if getattr(P, "cross_ok_cd", False):
-                def rider_cd():
-                    yield self._adam(P, "reconstruction", self._slab_notes, part="dec", ride=True, first=True)
-                    return (yield from dec.forward_steps(D, z_s, P.m_dec[2]))
-                host = self._then(steps, lambda: self._adam(P, "reconstruction", self._slab_notes, part="enc", ride=True,
-                                                            first=False), first)
-                _, dec_fwd = enc.lockstep(host, rider_cd(), finish_rider=False)
-            else:
-                enc.drive(steps, first)
-                self._adam(P, "reconstruction", self._slab_notes)
+            dec_fwd = self._cross(P, "CD", Pass(enc.backward_steps(E, P.spec, P.m_enc[2], P.dstyles, pending=left)),
+                                  "reconstruction", ("dec", "enc"), Pass(dec.forward_steps(D, z_s, P.m_dec[2])), carry=True)
         else:
             enc.backward(E, P.spec, P.m_enc[2], P.dstyles, pending=left)
             self._adam(P, "reconstruction", self._slab_notes)
@@ -1147,12 +1119,8 @@ class StepEngine:
             # the encoder forward whose result the reference does not use (BN stats + RNG only) and the decoder
             # forward, which only needs z_sample, in lockstep: one launch per pair of block kernels
             if dec_fwd is None:
-                dec_fwd = dec.forward_steps(D, z_s, P.m_dec[2])
-            if not (isinstance(dec_fwd, tuple) and dec_fwd[0] is None):
-                _, out = enc.forward_pair(enc.forward_steps(E, P.spec, P.m_enc[3]), dec_fwd)
-            else:
-                enc.forward(E, P.spec, P.m_enc[3])
-                out = dec_fwd[1]
+                dec_fwd = Pass(dec.forward_steps(D, z_s, P.m_dec[2]))
+            _, out = enc.forward_pair(Pass(enc.forward_steps(E, P.spec, P.m_enc[3])), dec_fwd)
         else:
             with self.aux_branch():                 # ... or on the auxiliary stream, beside the decoder forward
                 enc.forward(E, P.spec, P.m_enc[3])
@@ -1165,34 +1133,18 @@ class StepEngine:
         # state only.  Once the decoder's first block launch has carried the encoder's last weight-gradient tasks, the
         # encoder's half of this phase's update and then the encoder forward ride in the decoder backward's launches;
         # the decoder's half of the update follows.
-        cross = crossable and "DE" in across and smooth and left is not None
-        styles_e = None
-        if cross:
-            steps = dec.backward_steps(D, z_s, P.m_dec[2], P.dspec, None, pending=left)
-            first = next(steps)                  # (the head's backward has been launched inline)
-            first = steps.send(ops.launch_item(first[0], first[1]))      # block_bwd_b_wgrad: the encoder's gradients are complete
-            # Both halves must choose the kernel one launch over the range would: that needs more than 16 slabs somewhere
-            # in the ENCODER's slice already (the decoder's counts are not all known on the first, eager emission)
-            if record:
-                r0, r1 = self.arena.ranges["enc"]
-                P.cross_ok = int(self._slab_notes[r0 // 64:r1 // 64].max()) > 16
-            if getattr(P, "cross_ok", False):
-                def rider():
-                    yield self._adam(P, "mutual_info", self._slab_notes, part="enc", ride=True)
-                    return (yield from enc.forward_steps(E, P.spec, P.m_enc[5]))
-                _, styles_e = enc.lockstep(steps, rider(), first)
-                self._adam(P, "mutual_info", self._slab_notes, part="dec")
-            else:
-                enc.drive(steps, first)
-                self._adam(P, "mutual_info", self._slab_notes)
+        enc_fwd = None
+        if crossable and "DE" in across and smooth and left is not None:
+            enc_fwd = self._cross(P, "DE", Pass(dec.backward_steps(D, z_s, P.m_dec[2], P.dspec, None, pending=left)),
+                                  "mutual_info", ("enc", "dec"), Pass(enc.forward_steps(E, P.spec, P.m_enc[5])), carry=False)
         else:
             dec.backward(D, z_s, P.m_dec[2], P.dspec, None, pending=left)
             self._adam(P, "mutual_info", self._slab_notes)
         # ---- phase E: smoothness (:189-200); encoder gradients are discarded by the reference
         if smooth:
             self._begin_phase(record)
-            # (its gradients are discarded: no backward; `styles_e`: it has already run, beside phase D's decoder backward)
-            styles = styles_e if styles_e is not None else enc.forward(E, P.spec, P.m_enc[5])
+            # (its gradients are discarded: no backward; `enc_fwd`: it has already run, beside phase D's decoder backward)
+            styles = enc_fwd.result if enc_fwd is not None else enc.forward(E, P.spec, P.m_enc[5])
             out = dec.forward(D, styles, P.m_dec[3])
             ops.smooth_loss_fwd_bwd(out, b, self.L, self.taps, P.lpart, P.dout, fin=(1.0, lo, 4, -1, P.ticket))
             dec.backward(D, styles, P.m_dec[3], P.dout, None)

@@ -17,9 +17,10 @@ import os
 import torch
 from torch import nn
 
-from . import ops
+from . import ops, schedule
 from ._lib import (IN_NONE, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS, OUT_RELU, G_DIRECT,
                    RAAE_MAX_PARTS)
+from .schedule import Pass
 
 
 def _conv_desc(m, Lin):
@@ -57,8 +58,7 @@ class CompactNet:
         self.fused = bool(eng.cfg.get("fused_blocks", True))
         self.blocks = []
         if kind == "enc":
-            L = module.lin3.in_features * 8      # dim_in = 256: three blocks 256 -> 64 -> 16 -> 8, 4 channels
-            L = module.main[0].fc1.in_features
+            L = module.main[0].fc1.in_features       # dim_in = 256: three blocks 256 -> 64 -> 16 -> 8, 4 channels
             for m in module.main:
                 blk = Block(m, L)
                 self.blocks.append(blk)
@@ -149,7 +149,7 @@ class CompactNet:
             return self.eng.tape.view(masks[i][0], *masks[i][1])
         return None
 
-    def _cw(self, go, b, cv, view, conv, prelu, tag=0):
+    def _cw(self, go, b, cv, view, conv, prelu):
         """conv parameter gradients -> slabs; records the slab count of every tensor written."""
         eng = self.eng
         ps = [conv.weight, conv.bias] + ([prelu.weight] if prelu is not None else [])
@@ -158,7 +158,7 @@ class CompactNet:
                                      eng.gslab(prelu.weight) if prelu is not None else None, eng.arena.n)
         eng.note_slabs(ps, ns)
 
-    def _lw(self, go, b, Cc, E, view, Lin, lin, prelu, tag=0):
+    def _lw(self, go, b, Cc, E, view, Lin, lin, prelu):
         eng = self.eng
         with eng.side_stream():
             ns = ops.lenlin_bwd_weight(go, b, Cc, E, view, Lin, eng.gslab(lin.weight), eng.gslab(lin.bias),
@@ -168,54 +168,19 @@ class CompactNet:
     # ------------------------------------------------------------------ forward
     def forward(self, ws, x, masks, train=True):
         """One forward pass, every launch on its own."""
-        steps = self.forward_steps(ws, x, masks, train)
-        try:
-            kind, args, nbytes = next(steps)
-            while True:
-                kind, args, nbytes = steps.send(ops.launch_item(kind, args))
-        except StopIteration as done:
-            return done.value
+        return schedule.run(Pass(self.forward_steps(ws, x, masks, train)))
 
     @staticmethod
     def forward_pair(first, second):
-        """Two independent forward passes (``forward_steps`` generators, the ENCODER's first) in lockstep: while both
-        are at the same phase of a fused block the two kernels share one launch (raae_block_fwd_a2 / _b2), and the
-        decoder's head rides in an encoder block launch that has an instance for it (raae_co_launch).  ``second`` may be
-        ``(generator, item)``: a forward pass that has already begun (``lockstep(..., finish_rider=False)``) and the item
-        it is waiting at.  Returns the two outputs."""
-        started = isinstance(second, tuple)
-        gens, cur, out = [first, second[0] if started else second], [None, second[1] if started else None], [None, None]
-        for j in ((0,) if started else (0, 1)):
-            try:
-                cur[j] = next(gens[j])
-            except StopIteration as done:
-                out[j], gens[j] = done.value, None
-
-        def advance(j, n):
-            try:
-                cur[j] = gens[j].send(n)
-            except StopIteration as done:
-                out[j], gens[j], cur[j] = done.value, None, None
-        while gens[0] is not None or gens[1] is not None:
-            if gens[0] is not None and gens[1] is not None and cur[0][0] == cur[1][0]:
-                n1, n2 = ops.block_fwd_pair(cur[0][0], cur[0][1], cur[1][1])
-                advance(0, n1)
-                advance(1, n2)
-                continue
-            if (gens[0] is not None and gens[1] is not None and cur[1][0] == "head" and
-                    ops.co_pairable(cur[0][0], cur[0][1], "head", cur[1][1])):
-                n1, n2 = ops.co_launch(cur[0][0], cur[0][1], "head", cur[1][1])
-                advance(0, n1)
-                advance(1, n2)
-                continue
-            j = 0 if gens[0] is not None else 1
-            advance(j, ops.launch_item(cur[j][0], cur[j][1]))
-        return out[0], out[1]
+        """Two independent forward passes (``schedule.Pass`` over ``forward_steps``, the ENCODER's first) in lockstep
+        (``schedule.share_blocks``).  ``second`` may have begun as the rider of a backward pass, or have ended there.
+        Returns the two outputs."""
+        return schedule.lockstep(first, second, schedule.share_blocks)
 
     def forward_steps(self, ws, x, masks, train=True):
-        """Generator form of the forward pass: yields ``(phase, args, algorithmic bytes)`` at every fused-block
-        launch and expects the launch's partial-row count back, and ``("head", launch, 0)`` at the decoder's head when
-        the blocks are fused; everything else is launched inline."""
+        """Generator form of the forward pass (``schedule``): yields ``(phase, args)`` at every fused-block launch and
+        expects the launch's partial-row count back, and ``("head", launch)`` at the decoder's head when the blocks are
+        fused; everything else is launched inline."""
         b = ws.b
         X, pX, nX = x, None, 0                # block input (raw), statistics of it
         for i, (k, w) in enumerate(zip(self.blocks, ws.blk)):
@@ -230,7 +195,7 @@ class CompactNet:
                 # two kernels per block: everything that only needs bn1, then everything that needs bn2 / bn_excit
                 mask_i = self._mask(masks, i, train)
                 n1 = yield ("a", ops.block_fwd_a_args(vR(True), mask_i, b, k, m, w.T1, w.Sh, w.E1, w.E2, w.pT1,
-                                                      w.pE2 if k.cve is not None else None), 0)
+                                                      w.pE2 if k.cve is not None else None))
                 w.nT1 = w.nE2 = n1
                 v1 = ops.make_view(w.T1, m.relu1.weight, self._bn(m.bn2, w.pT1, w.nT1, b * k.L1, train, True))
                 if k.cve is not None:
@@ -239,7 +204,7 @@ class CompactNet:
                 else:
                     ve2 = ops.make_view(w.E2, m.relu_excit_2.weight)
                 w.nY = yield ("b", ops.block_fwd_b_args(v1, ve2, vR(False) if k.cvs is None else None, b, k, m, w.Sh,
-                                                        w.T2, w.E3, w.Y, w.pY), 0)
+                                                        w.T2, w.E3, w.Y, w.pY))
                 X, pX, nX = w.Y, w.pY, w.nY
                 continue
             w.nT1 = ops.conv_fwd(vR(True), b, k.cv1, m.conv1.weight, m.conv1.bias, w.T1, OUT_STATS_PRELU,
@@ -275,7 +240,7 @@ class CompactNet:
             if self.pairable:
                 # the head as an item: it may ride in a launch of the forward pass this one runs beside (forward_pair)
                 yield ("head", ops.conv_fwd_item(vf, b, self.cvf, self.conv_f.weight, self.conv_f.bias,
-                                                 ws.spec.view(b, 1, self.out_dim), self.act), 0)
+                                                 ws.spec.view(b, 1, self.out_dim), self.act))
             else:
                 ops.conv_fwd(vf, b, self.cvf, self.conv_f.weight, self.conv_f.bias, ws.spec.view(b, 1, self.out_dim),
                              OUT_RAW, None, None, self.act)
@@ -287,52 +252,7 @@ class CompactNet:
     def backward(self, ws, x, masks, g_out, dx_in=None, pending=None, keep_pending=False):
         """``pending``: weight-gradient tasks another network's backward left over (its return value with
         ``keep_pending``): they ride in this network's first fused launch instead of a launch of their own."""
-        return self.drive(self.backward_steps(ws, x, masks, g_out, dx_in, pending, keep_pending))
-
-    @staticmethod
-    def drive(steps, first=None):
-        """Run a generator of launches (``forward_steps`` / ``backward_steps``) to its end, every launch on its own;
-        ``first``: the item it has already yielded.  Returns the generator's result."""
-        try:
-            item = next(steps) if first is None else first
-            while True:
-                item = steps.send(ops.launch_item(item[0], item[1]))
-        except StopIteration as done:
-            return done.value
-
-    @staticmethod
-    def lockstep(main, rider, first=None, finish_rider=True):
-        """Two independent generators of launches in lockstep: while both have a launch ready that the two-body
-        launch takes as ONE (``ops.co_pairable``: ``main`` a backward pass and what ends it, ``rider`` whatever may run
-        beside it) the two share that launch (raae_co_launch); a launch of ``main`` that takes no rider goes alone and the
-        rider waits for the next one, and whichever generator outlives the other runs the rest alone.  ``first``: the item
-        ``main`` has already yielded.  Returns the two results; with ``finish_rider=False`` it returns as soon as ``main``
-        has ended and the rider's part of the result is ``(generator, the item it waits at)`` -- what ``forward_pair``
-        takes as its second pass -- or ``(None, result)`` if it has ended too."""
-        gens, cur, out = [main, rider], [first, None], [None, None]
-
-        def advance(j, n, start=False):
-            try:
-                cur[j] = next(gens[j]) if start else gens[j].send(n)
-            except StopIteration as done:
-                out[j], gens[j], cur[j] = done.value, None, None
-        if first is None:
-            advance(0, None, True)
-        advance(1, None, True)
-        while gens[0] is not None or gens[1] is not None:
-            if gens[0] is None and not finish_rider:
-                return out[0], (gens[1], cur[1])
-            if gens[0] is not None and gens[1] is not None:
-                if ops.co_pairable(cur[0][0], cur[0][1], cur[1][0], cur[1][1]):
-                    n1, n2 = ops.co_launch(cur[0][0], cur[0][1], cur[1][0], cur[1][1])
-                    advance(1, n2)       # (the rider first: what it launches inline next must not wait for `main`'s host work)
-                    advance(0, n1)
-                    continue
-                j = 1 if cur[1][0] == "adam" else 0      # (an update that cannot ride goes first: the rest waits for it)
-            else:
-                j = 0 if gens[0] is not None else 1
-            advance(j, ops.launch_item(cur[j][0], cur[j][1]))
-        return out[0], (out[1] if finish_rider else (None, out[1]))
+        return schedule.run(Pass(self.backward_steps(ws, x, masks, g_out, dx_in, pending, keep_pending)))
 
     def backward_steps(self, ws, x, masks, g_out, dx_in=None, pending=None, keep_pending=False):
         """Generator form of the backward pass: yields ``(kind, argument block)`` at every launch of the fused block

@@ -815,8 +815,8 @@ def conv_fwd_item(view, B, cv, w, bias, out, act):
     return launch
 
 
-# what a generator of launches (nets_conv.forward_steps / backward_steps, the engine's Adam updates) yields as its first
-# two items: ("a" | "b" | "head" | "bwd_a" | "bwd_b" | "wgrad" | "adam", argument block)
+# what a generator of launches (nets_conv.forward_steps / backward_steps, the engine's Adam updates; schedule.py) yields:
+# ("a" | "b" | "head" | "bwd_a" | "bwd_b" | "wgrad" | "adam", argument block)
 _CO_KIND = {"a": _lib.CO_FWD_A, "b": _lib.CO_FWD_B, "bwd_a": _lib.CO_BWD_A}
 
 
