@@ -822,7 +822,7 @@ __device__ __forceinline__ int conv_kind(const raae_conv_t& cv) {
 typedef raae_block_bwd_b_t BlockBwdBArgs;
 
 // `bx` of `gx`: the workgroup's index / count among the workgroups that run this block's backward phase B (the
-// whole grid of block_bwd_b_kernel, the leading range of block_bwd_b_wgrad_kernel)
+// whole grid of block_bwd_b_kernel, the leading range of co_kernel<CoBwdB<KB>, CoWgrad<KW>>)
 template <int KIND, bool BIG = false>        // see block_fwd_a_kernel
 __device__ __forceinline__ void block_bwd_b_body(const BlockBwdBArgs& a, const int bx, const int gx, float* dyn) {
 #define SH(f) (KIND >= 0 ? kBlk[KIND < 0 ? 0 : KIND].f : a.f)

@@ -849,18 +849,6 @@ static int prep_block_fwd_a(const raae_block_fwd_a_t* in, raae_block_fwd_a_t& a,
     return 0;
 }
 
-extern "C" int raae_block_fwd_a(const raae_block_fwd_a_t* in, int* nparts, void* stream) {
-    raae_block_fwd_a_t a;
-    int grid, kind;
-    size_t lds;
-    const int rc = prep_block_fwd_a(in, a, grid, lds, kind);
-    if (rc) return rc;
-    if (nparts) *nparts = grid;
-    const bool big = use_big(a.B, kind, kFamFwdA);
-    RAAE_LAUNCH_KIND_BIG(block_fwd_a_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a)
-    RAAE_LAUNCH_RET();
-}
-
 static int prep_block_fwd_b(const raae_block_fwd_b_t* in, raae_block_fwd_b_t& a, int& grid, size_t& lds, int& kind) {
     RAAE_CHECK_ARG(in && in->B > 0 && in->Cin >= 1 && in->Cin <= CT_MAXCH && in->Cout >= 1 && in->Cout <= CT_MAXCH);
     RAAE_CHECK_ARG(view_ok(&in->vT1, in->Cout) && view_ok(&in->vE2, in->Cin) && conv_ok(&in->cv2));
@@ -883,134 +871,7 @@ static int prep_block_fwd_b(const raae_block_fwd_b_t* in, raae_block_fwd_b_t& a,
     return 0;
 }
 
-extern "C" int raae_block_fwd_b(const raae_block_fwd_b_t* in, int* nparts, void* stream) {
-    raae_block_fwd_b_t a;
-    int grid, kind;
-    size_t lds;
-    const int rc = prep_block_fwd_b(in, a, grid, lds, kind);
-    if (rc) return rc;
-    if (nparts) *nparts = grid;
-    const bool big = use_big(a.B, kind, kFamFwdB);
-    RAAE_LAUNCH_KIND_BIG(block_fwd_b_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a)
-    RAAE_LAUNCH_RET();
-}
-
-// The same forward phase of TWO residual blocks that do not depend on each other (one of the encoder, one of the
-// decoder: the forward chain whose result the reference throws away runs beside a forward chain that is needed)
-// in ONE launch: workgroups [0, n1) run the first block, the rest the second.
-struct FwdA2Args { BlockFwdAArgs x; BlockFwdAArgs y; int n1; };
-struct FwdB2Args { BlockFwdBArgs x; BlockFwdBArgs y; int n1; };
-template <int K1, int K2>
-__global__ __launch_bounds__(256) void block_fwd_a2_kernel(FwdA2Args k) {
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ BlockFwdAArgs sa;
-    const int n1 = k.n1;
-    if ((int)blockIdx.x < n1) {
-        const BlockFwdAArgs& a = raae::args_to_lds_at(&sa, (int)offsetof(FwdA2Args, x));
-        block_fwd_a_body<K1>(a, blockIdx.x, n1, dyn);
-    } else {
-        const BlockFwdAArgs& a = raae::args_to_lds_at(&sa, (int)offsetof(FwdA2Args, y));
-        block_fwd_a_body<K2>(a, blockIdx.x - n1, gridDim.x - n1, dyn);
-    }
-}
-template <int K1, int K2>
-__global__ __launch_bounds__(256) void block_fwd_b2_kernel(FwdB2Args k) {
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ BlockFwdBArgs sa;
-    const int n1 = k.n1;
-    if ((int)blockIdx.x < n1) {
-        const BlockFwdBArgs& a = raae::args_to_lds_at(&sa, (int)offsetof(FwdB2Args, x));
-        block_fwd_b_body<K1>(a, blockIdx.x, n1, dyn);
-    } else {
-        const BlockFwdBArgs& a = raae::args_to_lds_at(&sa, (int)offsetof(FwdB2Args, y));
-        block_fwd_b_body<K2>(a, blockIdx.x - n1, gridDim.x - n1, dyn);
-    }
-}
-
-template <int K1, int K2>
-__global__ __launch_bounds__(256) void block_fwd_a2_kernel_m(const FwdA2Args* table) {      // one trial per grid plane
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ BlockFwdAArgs sa;
-    const FwdA2Args* k = table + blockIdx.z;
-    const int n1 = k->n1;
-    if ((int)blockIdx.x < n1) {
-        const BlockFwdAArgs& a = raae::args_from_ptr(&sa, &k->x);
-        block_fwd_a_body<K1>(a, blockIdx.x, n1, dyn);
-    } else {
-        const BlockFwdAArgs& a = raae::args_from_ptr(&sa, &k->y);
-        block_fwd_a_body<K2>(a, blockIdx.x - n1, gridDim.x - n1, dyn);
-    }
-}
-template <int K1, int K2>
-__global__ __launch_bounds__(256) void block_fwd_b2_kernel_m(const FwdB2Args* table) {
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    __shared__ BlockFwdBArgs sa;
-    const FwdB2Args* k = table + blockIdx.z;
-    const int n1 = k->n1;
-    if ((int)blockIdx.x < n1) {
-        const BlockFwdBArgs& a = raae::args_from_ptr(&sa, &k->x);
-        block_fwd_b_body<K1>(a, blockIdx.x, n1, dyn);
-    } else {
-        const BlockFwdBArgs& a = raae::args_from_ptr(&sa, &k->y);
-        block_fwd_b_body<K2>(a, blockIdx.x - n1, gridDim.x - n1, dyn);
-    }
-}
-
-// instances: encoder block i beside decoder block i of the 256-point networks, and encoder block 0 beside the decoder's
-// last block (a decoder forward that began in the launches of the phase before: StepEngine.emit_step); anything else:
-// two launches
-#define RAAE_FWD_PAIRS(KERNEL) \
-    if (k1 == 0 && k2 == 6) { raae::launch(KERNEL<0, 6>, KERNEL##_m<0, 6>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); } \
-    if (k1 == 0 && k2 == 3) { raae::launch(KERNEL<0, 3>, KERNEL##_m<0, 3>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); } \
-    if (k1 == 1 && k2 == 4) { raae::launch(KERNEL<1, 4>, KERNEL##_m<1, 4>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); } \
-    if (k1 == 2 && k2 == 5) { raae::launch(KERNEL<2, 5>, KERNEL##_m<2, 5>, grid, dim3(256), lds, (hipStream_t)stream, k); RAAE_LAUNCH_RET(); }
-
-extern "C" int raae_block_fwd_a2(const raae_block_fwd_a_t* x, const raae_block_fwd_a_t* y, int* nparts_x, int* nparts_y,
-                                 void* stream) {
-    static thread_local FwdA2Args k;
-    int g1, g2, k1, k2;
-    size_t l1, l2;
-    int rc = prep_block_fwd_a(x, k.x, g1, l1, k1);
-    if (rc) return rc;
-    rc = prep_block_fwd_a(y, k.y, g2, l2, k2);
-    if (rc) return rc;
-    if (nparts_x) *nparts_x = g1;
-    if (nparts_y) *nparts_y = g2;
-    k.n1 = g1;
-    const size_t lds = l1 > l2 ? l1 : l2;
-    const dim3 grid(g1 + g2);
-    RAAE_FWD_PAIRS(block_fwd_a2_kernel)
-    { const int kind = k1; const raae_block_fwd_a_t& a = k.x; const bool big = use_big(a.B, kind, kFamFwdA);
-      RAAE_LAUNCH_KIND_BIG(block_fwd_a_kernel, dim3(g1), dim3(256), l1, (hipStream_t)stream, a) }
-    { const int kind = k2; const raae_block_fwd_a_t& a = k.y; const bool big = use_big(a.B, kind, kFamFwdA);
-      RAAE_LAUNCH_KIND_BIG(block_fwd_a_kernel, dim3(g2), dim3(256), l2, (hipStream_t)stream, a) }
-    RAAE_LAUNCH_RET();
-}
-
-extern "C" int raae_block_fwd_b2(const raae_block_fwd_b_t* x, const raae_block_fwd_b_t* y, int* nparts_x, int* nparts_y,
-                                 void* stream) {
-    static thread_local FwdB2Args k;
-    int g1, g2, k1, k2;
-    size_t l1, l2;
-    int rc = prep_block_fwd_b(x, k.x, g1, l1, k1);
-    if (rc) return rc;
-    rc = prep_block_fwd_b(y, k.y, g2, l2, k2);
-    if (rc) return rc;
-    if (nparts_x) *nparts_x = g1;
-    if (nparts_y) *nparts_y = g2;
-    k.n1 = g1;
-    const size_t lds = l1 > l2 ? l1 : l2;
-    const dim3 grid(g1 + g2);
-    RAAE_FWD_PAIRS(block_fwd_b2_kernel)
-    { const int kind = k1; const raae_block_fwd_b_t& a = k.x; const bool big = use_big(a.B, kind, kFamFwdB);
-      RAAE_LAUNCH_KIND_BIG(block_fwd_b_kernel, dim3(g1), dim3(256), l1, (hipStream_t)stream, a) }
-    { const int kind = k2; const raae_block_fwd_b_t& a = k.y; const bool big = use_big(a.B, kind, kFamFwdB);
-      RAAE_LAUNCH_KIND_BIG(block_fwd_b_kernel, dim3(g2), dim3(256), l2, (hipStream_t)stream, a) }
-    RAAE_LAUNCH_RET();
-}
-#undef RAAE_FWD_PAIRS
-
-// checks + launch geometry of backward phase B (shared by raae_block_bwd_b and raae_block_bwd_b_wgrad)
+// checks + launch geometry of backward phase B
 static int prep_block_bwd_b(const raae_block_bwd_b_t* in, raae_block_bwd_b_t& a, int& grid, size_t& lds, int& kind) {
     RAAE_CHECK_ARG(in && in->B > 0 && in->Cin >= 1 && in->Cin <= CT_MAXCH && in->Cout >= 1 && in->Cout <= CT_MAXCH);
     RAAE_CHECK_ARG(in->gy.g && (!in->gy.has_bn || (in->gy.u && in->gy.g_partials && in->gy.bn.partials &&
@@ -1037,19 +898,7 @@ static int prep_block_bwd_b(const raae_block_bwd_b_t* in, raae_block_bwd_b_t& a,
     return 0;
 }
 
-extern "C" int raae_block_bwd_b(const raae_block_bwd_b_t* in, int* nparts, void* stream) {
-    raae_block_bwd_b_t a;
-    int grid, kind;
-    size_t lds;
-    const int rc = prep_block_bwd_b(in, a, grid, lds, kind);
-    if (rc) return rc;
-    if (nparts) *nparts = grid;
-    const bool big = use_big(a.B, kind, kFamBwdB);
-    RAAE_LAUNCH_KIND_BIG(block_bwd_b_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a)
-    RAAE_LAUNCH_RET();
-}
-
-// checks + launch geometry of backward phase A (shared by raae_block_bwd_a and raae_co_launch)
+// checks + launch geometry of backward phase A
 static int prep_block_bwd_a(const raae_block_bwd_a_t* in, raae_block_bwd_a_t& a, int& grid, size_t& lds, int& kind) {
     RAAE_CHECK_ARG(in && in->B > 0 && in->Cin >= 1 && in->Cin <= CT_MAXCH && in->Cout >= 1 && in->Cout <= CT_MAXCH);
     RAAE_CHECK_ARG(grad_ok(&in->g1, in->Cout) && in->g1.has_bn && in->g1.raw && in->g1.slope);
@@ -1079,23 +928,25 @@ static int prep_block_bwd_a(const raae_block_bwd_a_t* in, raae_block_bwd_a_t& a,
     return 0;
 }
 
-extern "C" int raae_block_bwd_a(const raae_block_bwd_a_t* in, int* nparts, void* stream) {
-    raae_block_bwd_a_t a;
-    int grid, kind;
-    size_t lds;
-    const int rc = prep_block_bwd_a(in, a, grid, lds, kind);
-    if (rc) return rc;
-    if (nparts) *nparts = grid;
-    const bool big = use_big(a.B, kind, kFamBwdA);
-    RAAE_LAUNCH_KIND_BIG(block_bwd_a_kernel, dim3(grid), dim3(256), lds, (hipStream_t)stream, a)
-    RAAE_LAUNCH_RET();
-}
-
 // workgroups per weight-gradient task (= slabs it writes); 64 -> 128: +2 % at B=256, +18 % at B=4096
 static const int kWgradTaskGridDefault = 128;
 // tuning knobs (environment, read once): RAAE_WGRAD_GRID workgroups per task, RAAE_WGRAD_S samples per group (0: automatic)
 static const int kWgradTaskGrid = env_int("RAAE_WGRAD_GRID", kWgradTaskGridDefault);
 static const int kWgradForceS = env_int("RAAE_WGRAD_S", 0);
+// one task of prep_block_wgrad after its pick_S: the forced / capped samples per group, its groups and workgroups
+// (= the slabs it writes) and its row of the task table
+template <class T>
+static void wgrad_task(WgradMultiArgs& m, T& t, int B, long per, int task_grid, int is_conv, int idx, int* nslab,
+                       int& total, size_t& dyn) {
+    if (kWgradForceS > 0 && B >= RAAE_BIG_ROWS) { t.S = kWgradForceS; const long cap = (36 * 1024) / per; if (t.S > cap) t.S = (int)cap; if (t.S < 1) t.S = 1; }
+    { const int scap = (B + task_grid - 1) / task_grid; if (t.S > scap) t.S = scap; }   // parallelism from workgroups, not from samples per group
+    t.ngroups = (B + t.S - 1) / t.S;
+    const int grid = t.ngroups < task_grid ? t.ngroups : task_grid;
+    m.first[m.ntask] = total; m.is_conv[m.ntask] = is_conv; m.idx[m.ntask] = idx; nslab[m.ntask] = grid;
+    total += grid; ++m.ntask;
+    const size_t d = sizeof(float) * (size_t)t.S * per;
+    if (d > dyn) dyn = d;
+}
 // checks + task table + launch geometry of a block's weight-gradient tasks; `m` is filled
 static int prep_block_wgrad(const raae_block_wgrad_t* in, int* nslab, WgradMultiArgs& m, int& total_out, size_t& dyn_out,
                             int& kind_out) {
@@ -1105,7 +956,7 @@ static int prep_block_wgrad(const raae_block_wgrad_t* in, int* nslab, WgradMulti
     int total = 0;
     size_t dyn = 0;
     // raae_tile_hint: a caller that launches T trials at once gets T times the workgroups anyway
-    const int kWgradTaskGrid = ::kWgradTaskGrid / g_tile_mult > 16 ? ::kWgradTaskGrid / g_tile_mult : 16;
+    const int task_grid = kWgradTaskGrid / g_tile_mult > 16 ? kWgradTaskGrid / g_tile_mult : 16;
     for (int i = 0; i < in->n_conv; ++i) {
         const raae_wgrad_conv_t& c = in->conv[i];
         const raae_conv_t* cv = &c.cv;
@@ -1118,14 +969,7 @@ static int prep_block_wgrad(const raae_block_wgrad_t* in, int* nslab, WgradMulti
         RAAE_CHECK_ARG(t.a.nw <= 1024 && per <= kTileBudget);
         t.slab_stride = in->slab_stride; t.sh_in = lg2(cv->Lin); t.sh_out = lg2(cv->Lout);
         t.S = pick_S(per, cv->transposed ? cv->Lin : cv->Lout, in->B, kTileBudget, 256);
-        if (kWgradForceS > 0 && in->B >= RAAE_BIG_ROWS) { t.S = kWgradForceS; const long cap = (36 * 1024) / per; if (t.S > cap) t.S = (int)cap; if (t.S < 1) t.S = 1; }
-        { const int scap = (in->B + kWgradTaskGrid - 1) / kWgradTaskGrid; if (t.S > scap) t.S = scap; }   // parallelism from workgroups, not from samples per group
-        t.ngroups = (in->B + t.S - 1) / t.S;
-        const int grid = t.ngroups < kWgradTaskGrid ? t.ngroups : kWgradTaskGrid;
-        m.first[m.ntask] = total; m.is_conv[m.ntask] = 1; m.idx[m.ntask] = i; nslab[m.ntask] = grid;
-        total += grid; ++m.ntask;
-        const size_t d = sizeof(float) * (size_t)t.S * per;
-        if (d > dyn) dyn = d;
+        wgrad_task(m, t, in->B, per, task_grid, 1, i, nslab, total, dyn);
     }
     for (int i = 0; i < in->n_lin; ++i) {
         const raae_wgrad_lin_t& c = in->lin[i];
@@ -1138,14 +982,7 @@ static int prep_block_wgrad(const raae_block_wgrad_t* in, int* nslab, WgradMulti
         RAAE_CHECK_ARG(per <= kTileBudget);
         t.slab_stride = in->slab_stride; t.sh_in = lg2(c.Lin); t.sh_e = lg2(c.E);
         t.S = pick_S(per, c.C, in->B, kTileBudget, 64);
-        if (kWgradForceS > 0 && in->B >= RAAE_BIG_ROWS) { t.S = kWgradForceS; const long cap = (36 * 1024) / per; if (t.S > cap) t.S = (int)cap; if (t.S < 1) t.S = 1; }
-        { const int scap = (in->B + kWgradTaskGrid - 1) / kWgradTaskGrid; if (t.S > scap) t.S = scap; }   // parallelism from workgroups, not from samples per group
-        t.ngroups = (in->B + t.S - 1) / t.S;
-        const int grid = t.ngroups < kWgradTaskGrid ? t.ngroups : kWgradTaskGrid;
-        m.first[m.ntask] = total; m.is_conv[m.ntask] = 0; m.idx[m.ntask] = i; nslab[m.ntask] = grid;
-        total += grid; ++m.ntask;
-        const size_t d = sizeof(float) * (size_t)t.S * per;
-        if (d > dyn) dyn = d;
+        wgrad_task(m, t, in->B, per, task_grid, 0, i, nslab, total, dyn);
     }
     m.first[m.ntask] = total;
     // shape-specialised instance: every conv task must be one of the convs of a known block shape
@@ -1167,87 +1004,11 @@ static int prep_block_wgrad(const raae_block_wgrad_t* in, int* nslab, WgradMulti
     return 0;
 }
 
-extern "C" int raae_block_wgrad(const raae_block_wgrad_t* in, int* nslab, void* stream) {
-    static thread_local WgradMultiArgs m;   // large (kernarg by value); per-thread host scratch, filled per call
-    int total, kind;
-    size_t dyn;
-    const int rc = prep_block_wgrad(in, nslab, m, total, dyn, kind);
-    if (rc) return rc;
-    const bool big = use_big(in->B, kind, kFamWgrad);
-    RAAE_LAUNCH_KIND_BIG(wgrad_multi_kernel, dim3(total), dim3(256), dyn, (hipStream_t)stream, m)
-    RAAE_LAUNCH_RET();
-}
-
-// Backward phase B of one residual block and ALL weight-gradient tasks of the block after it (whose data
-// gradients are complete) in ONE launch: workgroups [0, nb) run block_bwd_b, the rest the weight-gradient tasks.
-// The two are independent, so they overlap on the chip like parallel graph branches would -- without the
-// fork/join edges, which at 256-row batches cost as much as the kernels.
-struct BwdBWgradArgs { BlockBwdBArgs b; WgradMultiArgs w; int nb; };
-template <int KB, int KW>
-__global__ __launch_bounds__(256) void block_bwd_b_wgrad_kernel(BwdBWgradArgs k) {
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    const int nb = k.nb;
-    if ((int)blockIdx.x < nb) {
-        __shared__ BlockBwdBArgs sa;
-        const BlockBwdBArgs& a = raae::args_to_lds_at(&sa, (int)offsetof(BwdBWgradArgs, b));
-        block_bwd_b_body<KB>(a, blockIdx.x, nb, dyn);
-    } else {
-        __shared__ WgradMultiArgs sm;
-        const WgradMultiArgs& m = raae::args_to_lds_at(&sm, (int)offsetof(BwdBWgradArgs, w));
-        wgrad_multi_body<KW>(m, blockIdx.x - nb, dyn);
-    }
-}
-
-template <int KB, int KW>
-__global__ __launch_bounds__(256) void block_bwd_b_wgrad_kernel_m(const BwdBWgradArgs* table) {     // one trial per grid plane
-    extern __shared__ __attribute__((aligned(16))) float dyn[];
-    const BwdBWgradArgs* k = table + blockIdx.z;
-    const int nb = k->nb;
-    if ((int)blockIdx.x < nb) {
-        __shared__ BlockBwdBArgs sa;
-        const BlockBwdBArgs& a = raae::args_from_ptr(&sa, &k->b);
-        block_bwd_b_body<KB>(a, blockIdx.x, nb, dyn);
-    } else {
-        __shared__ WgradMultiArgs sm;
-        const WgradMultiArgs& m = raae::args_from_ptr(&sm, &k->w);
-        wgrad_multi_body<KW>(m, blockIdx.x - nb, dyn);
-    }
-}
-
-static int launch_bwd_b_wgrad(const BwdBWgradArgs& k, int kindb, int kindw, dim3 grid, size_t lds, hipStream_t stream) {
-    const dim3 block(256);
-    // instances: phase B of block i-1 beside the weight gradients of block i, for the block sequences of the
-    // 256-point networks (encoder 0,1,2; decoder 3,4,5,6); anything else runs the generic pair
-#define RAAE_PAIR(KB_, KW_) if (kindb == KB_ && kindw == KW_) { \
-        raae::launch(block_bwd_b_wgrad_kernel<KB_, KW_>, block_bwd_b_wgrad_kernel_m<KB_, KW_>, grid, block, lds, stream, k); RAAE_LAUNCH_RET(); }
-    RAAE_PAIR(0, 1) RAAE_PAIR(1, 2) RAAE_PAIR(3, 4) RAAE_PAIR(4, 5) RAAE_PAIR(5, 6)
-    RAAE_PAIR(2, 3) RAAE_PAIR(6, 0)      // across the networks: encoder's last block beside decoder block 0's tasks, and back
-    RAAE_PAIR(6, -1)                     // the decoder's head conv (a lone generic task) beside its last block
-#undef RAAE_PAIR
-    raae::launch(block_bwd_b_wgrad_kernel<-1, -1>, block_bwd_b_wgrad_kernel_m<-1, -1>, grid, block, lds, stream, k);
-    RAAE_LAUNCH_RET();
-}
-
-extern "C" int raae_block_bwd_b_wgrad(const raae_block_bwd_b_t* bin, const raae_block_wgrad_t* win, int* nparts,
-                                      int* nslab, void* stream) {
-    static thread_local BwdBWgradArgs k;
-    int gridb, kindb, total, kindw;
-    size_t ldsb, dynw;
-    int rc = prep_block_bwd_b(bin, k.b, gridb, ldsb, kindb);
-    if (rc) return rc;
-    rc = prep_block_wgrad(win, nslab, k.w, total, dynw, kindw);
-    if (rc) return rc;
-    if (nparts) *nparts = gridb;
-    k.nb = gridb;
-    const size_t lds = ldsb > dynw ? ldsb : dynw;
-    return launch_bwd_b_wgrad(k, kindb, kindw, dim3(gridb + total), lds, (hipStream_t)stream);
-}
-
-// ---- two independent bodies of this translation unit in ONE launch (the general form of block_fwd_a2_kernel) ----
+// ---- two independent bodies of this translation unit in ONE launch ----
 // Workgroups [0, n1) run X::body, the rest Y::body; each body sees its index among, and the number of, the workgroups
-// that run it, so it computes what its own kernel computes.  X / Y are tags over the existing bodies.  Used across a
-// phase boundary of the 256-row step: the decoder backward that ends the mutual-information
-// phase carries the encoder's half of that phase's Adam update and then the encoder forward of the smoothness phase.
+// that run it, so it computes what its own kernel computes.  X / Y are tags over the existing bodies.  The two are
+// independent, so they overlap on the chip like parallel graph branches would -- without the fork/join edges, which
+// at 256-row batches cost as much as the kernels.  co_pair below lists every instance.
 #include "raae_adam_body.inc"
 #define COMMA ,
 template <int K> struct CoFwdA {
@@ -1262,12 +1023,9 @@ template <int K> struct CoBwdA {
     typedef BlockBwdAArgs Args;
     static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) { block_bwd_a_body<K, false>(a, bx, gx, dyn); }
 };
-template <int KB, int KW> struct CoBwdBW {      // the two bodies of block_bwd_b_wgrad_kernel<KB, KW>
-    typedef BwdBWgradArgs Args;
-    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) {
-        if (bx < a.nb) block_bwd_b_body<KB>(a.b, bx, a.nb, dyn);
-        else wgrad_multi_body<KW>(a.w, bx - a.nb, dyn);
-    }
+template <int K> struct CoBwdB {
+    typedef BlockBwdBArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) { block_bwd_b_body<K>(a, bx, gx, dyn); }
 };
 template <bool CHK> struct CoAdam {             // adam_wide_kernel / adam_wide_chk_kernel (raae_optim.hip)
     typedef AdamChkArgs Args;
@@ -1277,7 +1035,7 @@ template <bool CHK> struct CoAdam {             // adam_wide_kernel / adam_wide_
                             c.nan_step, bx, gx);
     }
 };
-template <int KW> struct CoWgrad {               // wgrad_multi_kernel<KW>: the weight-gradient tasks that end a backward pass
+template <int KW> struct CoWgrad {               // wgrad_multi_kernel<KW>: all weight-gradient tasks of a block
     typedef WgradMultiArgs Args;
     static __device__ __forceinline__ void body(const Args& m, int bx, int, float* dyn) { wgrad_multi_body<KW>(m, bx, dyn); }
 };
@@ -1285,33 +1043,41 @@ template <int C> struct CoHeadFwd {              // head_fwd_kernel<C> (raae_hea
     typedef HeadFwdArgs Args;
     static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float*) { head_fwd_body<C>(a, bx, gx); }
 };
+// a pair as ONE body of a larger pair: co_kernel<CoBwdB<KB>, CoWgrad<KW>>'s two bodies and its argument block
+struct BwdBWgradArgs { BlockBwdBArgs b; WgradMultiArgs w; int nb; };
+template <int KB, int KW> struct CoBwdBW {
+    typedef BwdBWgradArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) {
+        if (bx < a.nb) block_bwd_b_body<KB>(a.b, bx, a.nb, dyn);
+        else wgrad_multi_body<KW>(a.w, bx - a.nb, dyn);
+    }
+};
 template <class X, class Y> struct CoArgs { typename X::Args x; typename Y::Args y; int n1; };
+template <class X, class Y> union CoSlot { typename X::Args x; typename Y::Args y; };     // a workgroup runs one of the two
 template <class X, class Y>
 __global__ __launch_bounds__(256) void co_kernel(CoArgs<X, Y> k) {
     extern __shared__ __attribute__((aligned(16))) float dyn[];
+    __shared__ __attribute__((aligned(16))) CoSlot<X, Y> s;
     const int n1 = k.n1;
     if ((int)blockIdx.x < n1) {
-        __shared__ typename X::Args sx;
-        const typename X::Args& a = raae::args_to_lds_at(&sx, (int)offsetof(CoArgs<X COMMA Y>, x));
+        const typename X::Args& a = raae::args_to_lds_at(&s.x, (int)offsetof(CoArgs<X COMMA Y>, x));
         X::body(a, blockIdx.x, n1, dyn);
     } else {
-        __shared__ typename Y::Args sy;
-        const typename Y::Args& a = raae::args_to_lds_at(&sy, (int)offsetof(CoArgs<X COMMA Y>, y));
+        const typename Y::Args& a = raae::args_to_lds_at(&s.y, (int)offsetof(CoArgs<X COMMA Y>, y));
         Y::body(a, blockIdx.x - n1, gridDim.x - n1, dyn);
     }
 }
 template <class X, class Y>
 __global__ __launch_bounds__(256) void co_kernel_m(const CoArgs<X, Y>* table) {      // one trial per grid plane
     extern __shared__ __attribute__((aligned(16))) float dyn[];
+    __shared__ __attribute__((aligned(16))) CoSlot<X, Y> s;
     const CoArgs<X, Y>* k = table + blockIdx.z;
     const int n1 = k->n1;
     if ((int)blockIdx.x < n1) {
-        __shared__ typename X::Args sx;
-        const typename X::Args& a = raae::args_from_ptr(&sx, &k->x);
+        const typename X::Args& a = raae::args_from_ptr(&s.x, &k->x);
         X::body(a, blockIdx.x, n1, dyn);
     } else {
-        __shared__ typename Y::Args sy;
-        const typename Y::Args& a = raae::args_from_ptr(&sy, &k->y);
+        const typename Y::Args& a = raae::args_from_ptr(&s.y, &k->y);
         Y::body(a, blockIdx.x - n1, gridDim.x - n1, dyn);
     }
 }
@@ -1324,18 +1090,23 @@ static void co_go(const typename X::Args& x, const typename Y::Args& y, int g1, 
     raae::launch(co_kernel<X, Y>, co_kernel_m<X, Y>, dim3(g1 + g2), dim3(256), lds, stream, k);
 }
 
-// one side of raae_co_launch after its checks: the prepared argument block, geometry and instance
+// One side of a launch after its checks: the prepared argument block, geometry and instance.  `big`: alone, the side
+// runs its large-batch instance (use_big; co_single launches that one).  `large`: 1024 rows or more on a side that has
+// no instance of its own to choose (RAAE_CO_BWD_B_WGRAD, RAAE_CO_HEAD_FWD).  Either keeps a side out of the `plain` rows.
+enum { kCoBwdB = 100 };     // phase B alone: a side of raae_block_bwd_b(_wgrad), not a kind of the C ABI
+static bool co_public(int kind) { return kind >= RAAE_CO_FWD_A && kind <= RAAE_CO_HEAD_FWD; }
 struct CoSide {
     int kind = -1, k = -1, kw = -1, grid = 0;
     size_t lds = 0;
-    bool big = false, chk = false, wide = false;
+    bool big = false, large = false, chk = false, wide = false;
     int max_nslab = 0;
-    BlockFwdAArgs fa; BlockFwdBArgs fb; BlockBwdAArgs ba; BwdBWgradArgs bw; AdamChkArgs ad; WgradMultiArgs wg; HeadFwdArgs hf;
+    BlockFwdAArgs fa; BlockFwdBArgs fb; BlockBwdAArgs ba; BlockBwdBArgs bb; BwdBWgradArgs bw; AdamChkArgs ad; WgradMultiArgs wg;
+    HeadFwdArgs hf;
     raae_co_conv_fwd_t cf;
 };
 static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
     RAAE_CHECK_ARG(args);
-    s.kind = kind;
+    s.kind = kind; s.big = s.large = false;
     int rc = 0;
     switch (kind) {
     case RAAE_CO_FWD_A:
@@ -1350,6 +1121,10 @@ static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
         rc = prep_block_bwd_a((const raae_block_bwd_a_t*)args, s.ba, s.grid, s.lds, s.k);
         if (!rc) s.big = use_big(s.ba.B, s.k, kFamBwdA);
         break;
+    case kCoBwdB:
+        rc = prep_block_bwd_b((const raae_block_bwd_b_t*)args, s.bb, s.grid, s.lds, s.k);
+        if (!rc) s.big = use_big(s.bb.B, s.k, kFamBwdB);
+        break;
     case RAAE_CO_BWD_B_WGRAD: {
         const raae_co_bwd_b_wgrad_t* p = (const raae_co_bwd_b_wgrad_t*)args;
         RAAE_CHECK_ARG(p->b && p->w && p->nslab);
@@ -1363,7 +1138,7 @@ static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
         if (nparts) *nparts = gb;
         s.grid = gb + total;
         s.lds = ldsb > dynw ? ldsb : dynw;
-        s.big = p->b->B >= RAAE_BIG_ROWS;       // (raae_block_bwd_b_wgrad itself has no large-batch pairs)
+        s.large = p->b->B >= RAAE_BIG_ROWS;
         return 0;
     }
     case RAAE_CO_ADAM: {
@@ -1394,14 +1169,14 @@ static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
         const raae_co_conv_fwd_t* p = (const raae_co_conv_fwd_t*)args;
         RAAE_CHECK_ARG(p->in && p->cv && conv_ok(p->cv) && view_ok(p->in, p->cv->Cin) && p->w && p->bias && p->out && p->B > 0);
         s.cf = *p;
-        s.k = -1; s.grid = 0; s.lds = 0; s.big = false;
+        s.k = -1; s.grid = 0; s.lds = 0;
         if (head_shape_ok(p->cv, p->in) && (reinterpret_cast<uintptr_t>(p->out) & 15) == 0) {     // as raae_conv_fwd
             HeadFwdArgs& h = s.hf;
             h.in = *p->in; h.B = p->B; h.L = p->cv->Lin; h.w = p->w; h.bias = p->bias; h.out = p->out; h.act = p->act;
             h.nq = p->B * (p->cv->Lin >> 2);
             s.k = p->cv->Cin;
             s.grid = head_grid(h.nq, p->cv->Cin <= 4 ? kHeadU : kHeadU / 2);
-            s.big = p->B >= RAAE_BIG_ROWS;
+            s.large = p->B >= RAAE_BIG_ROWS;
         }
         if (nparts) *nparts = 0;
         return 0;
@@ -1412,7 +1187,8 @@ static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
     if (!rc && nparts) *nparts = s.grid;
     return rc;
 }
-// a side on its own: the launch its own entry point makes
+static int co_run(const CoSide& x, const CoSide& y, hipStream_t st, bool entry);
+// a side on its own -- the only place that launches a body alone
 static int co_single(const CoSide& s, hipStream_t stream) {
     const int kind = s.k;
     const bool big = s.big;
@@ -1420,8 +1196,15 @@ static int co_single(const CoSide& s, hipStream_t stream) {
     case RAAE_CO_FWD_A: { const raae_block_fwd_a_t& a = s.fa; RAAE_LAUNCH_KIND_BIG(block_fwd_a_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
     case RAAE_CO_FWD_B: { const raae_block_fwd_b_t& a = s.fb; RAAE_LAUNCH_KIND_BIG(block_fwd_b_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
     case RAAE_CO_BWD_A: { const raae_block_bwd_a_t& a = s.ba; RAAE_LAUNCH_KIND_BIG(block_bwd_a_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
-    case RAAE_CO_BWD_B_WGRAD: return launch_bwd_b_wgrad(s.bw, s.k, s.kw, dim3(s.grid), s.lds, stream);
+    case kCoBwdB: { const raae_block_bwd_b_t& a = s.bb; RAAE_LAUNCH_KIND_BIG(block_bwd_b_kernel, dim3(s.grid), dim3(256), s.lds, stream, a) break; }
     case RAAE_CO_WGRAD: { const WgradMultiArgs& m = s.wg; RAAE_LAUNCH_KIND_BIG(wgrad_multi_kernel, dim3(s.grid), dim3(256), s.lds, stream, m) break; }
+    case RAAE_CO_BWD_B_WGRAD: {             // its two prepared halves as the pair raae_block_bwd_b_wgrad launches
+        static thread_local CoSide b, w;
+        b.kind = kCoBwdB; b.k = s.k; b.grid = s.bw.nb; b.bb = s.bw.b;
+        w.kind = RAAE_CO_WGRAD; w.k = s.kw; w.grid = s.grid - s.bw.nb; w.wg = s.bw.w;
+        b.lds = w.lds = s.lds;              // (the larger of the two: every such pair has a row, none runs alone)
+        return co_run(b, w, stream, true);
+    }
     case RAAE_CO_HEAD_FWD:
         return raae_conv_fwd(s.cf.in, s.cf.B, s.cf.cv, s.cf.w, s.cf.bias, s.cf.out, RAAE_OUT_RAW, nullptr, nullptr, nullptr,
                              s.cf.act, stream);
@@ -1437,59 +1220,141 @@ static int co_single(const CoSide& s, hipStream_t stream) {
     RAAE_LAUNCH_RET();
 }
 
-// the pair as ONE launch if it has an instance (`dry`: only say whether it has): 1, else 0
-static int co_pair(const CoSide& x, const CoSide& y, hipStream_t st, bool dry) {
+// The pair as ONE launch if it has an instance (`dry`: only say whether it has): 1, else 0.  Every two-body instance
+// of the conv networks is a row here; the first column says when the row applies.  All rows run the plain (not BIG)
+// bodies.
+//   plain -- only while neither side would run a large-batch instance alone or has 1024 rows without one (CoSide::big,
+//     ::large), so that a side computes with the instance it has alone.  The phase boundaries of the 256-point networks' 256-row step: the decoder
+//     backward (blocks 6, 5, 4, 3) carrying the encoder's Adam half and then the encoder forward (blocks 0, 1, 2); the
+//     encoder backward (blocks 2, 1, 0), its last weight-gradient tasks and the update behind it carrying the decoder's
+//     Adam half and then the decoder forward's blocks 3, 4, 5; the encoder forward's second block carrying the decoder's
+//     head.
+//   entry -- for the pair entry points (`entry`: raae_block_fwd_a2 / _b2 / _bwd_b_wgrad; not raae_co_launch, whose
+//     pairs run what the two sides run alone), at every row count.  The same forward phase of an encoder and a decoder block (raae_block_fwd_a2 / _b2:
+//     the forward chain whose result the reference throws away beside one that is needed): encoder block i beside
+//     decoder block i, and encoder block 0 beside the decoder's last block (a decoder forward that began in the launches
+//     of the phase before: StepEngine.emit_step).  Backward phase B of block i-1 beside all weight-gradient tasks of
+//     block i, whose data gradients are complete (raae_block_bwd_b_wgrad), along the block sequences (encoder 0, 1, 2;
+//     decoder 3, 4, 5, 6), across the networks (2 beside 3's tasks, 6 beside 0's), the decoder's head conv (a lone
+//     generic task) beside its last block, and the generic pair for anything else.
+// A pair without a row: two launches, x first.
+static int co_pair(const CoSide& x, const CoSide& y, hipStream_t st, bool dry, bool entry) {
     const size_t lds = x.lds > y.lds ? x.lds : y.lds;
-    if (x.big || y.big) return 0;
-    // instances, 256-point networks.  The decoder backward (blocks 6, 5, 4, 3) carrying the encoder's Adam half and then
-    // the encoder forward (blocks 0, 1, 2); the encoder backward (blocks 2, 1, 0), its last weight-gradient tasks and the
-    // update behind it carrying the decoder's Adam half and then the decoder forward's blocks 3, 4, 5; the encoder
-    // forward's second block carrying the decoder's head.  Anything else: two launches.
-#define RAAE_CO(XK, XCOND, XT, XF, YK, YCOND, YT, YF) if (x.kind == XK && (XCOND) && y.kind == YK && (YCOND)) { \
+    const bool plain = !(x.big || x.large || y.big || y.large);
+#define RAAE_CO(ROWS, XK, XCOND, XT, XF, YK, YCOND, YT, YF) if (ROWS && x.kind == XK && (XCOND) && y.kind == YK && (YCOND)) { \
         if (!dry) co_go<XT, YT>(x.XF, y.YF, x.grid, y.grid, lds, st); return 1; }
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
-    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 5 && x.kw == 6, CoBwdBW<5 COMMA 6>, bw, RAAE_CO_FWD_A, y.k == 0, CoFwdA<0>, fa)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 5, CoBwdA<5>, ba, RAAE_CO_FWD_B, y.k == 0, CoFwdB<0>, fb)
-    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 4 && x.kw == 5, CoBwdBW<4 COMMA 5>, bw, RAAE_CO_FWD_A, y.k == 1, CoFwdA<1>, fa)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 4, CoBwdA<4>, ba, RAAE_CO_FWD_B, y.k == 1, CoFwdB<1>, fb)
-    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 3 && x.kw == 4, CoBwdBW<3 COMMA 4>, bw, RAAE_CO_FWD_A, y.k == 2, CoFwdA<2>, fa)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 3, CoBwdA<3>, ba, RAAE_CO_FWD_B, y.k == 2, CoFwdB<2>, fb)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 2, CoBwdA<2>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 2, CoBwdA<2>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
-    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 1 && x.kw == 2, CoBwdBW<1 COMMA 2>, bw, RAAE_CO_FWD_A, y.k == 3, CoFwdA<3>, fa)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 1, CoBwdA<1>, ba, RAAE_CO_FWD_B, y.k == 3, CoFwdB<3>, fb)
-    RAAE_CO(RAAE_CO_BWD_B_WGRAD, x.k == 0 && x.kw == 1, CoBwdBW<0 COMMA 1>, bw, RAAE_CO_FWD_A, y.k == 4, CoFwdA<4>, fa)
-    RAAE_CO(RAAE_CO_BWD_A, x.k == 0, CoBwdA<0>, ba, RAAE_CO_FWD_B, y.k == 4, CoFwdB<4>, fb)
-    RAAE_CO(RAAE_CO_WGRAD, x.k == 0, CoWgrad<0>, wg, RAAE_CO_FWD_A, y.k == 5, CoFwdA<5>, fa)
-    RAAE_CO(RAAE_CO_ADAM, x.wide && x.chk, CoAdam<true>, ad, RAAE_CO_FWD_B, y.k == 5, CoFwdB<5>, fb)
-    RAAE_CO(RAAE_CO_ADAM, x.wide && !x.chk, CoAdam<false>, ad, RAAE_CO_FWD_B, y.k == 5, CoFwdB<5>, fb)
-    RAAE_CO(RAAE_CO_FWD_A, x.k == 1, CoFwdA<1>, fa, RAAE_CO_HEAD_FWD, y.k == 4, CoHeadFwd<4>, hf)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 6, CoBwdA<6>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
+    RAAE_CO(plain, RAAE_CO_BWD_B_WGRAD, x.k == 5 && x.kw == 6, CoBwdBW<5 COMMA 6>, bw, RAAE_CO_FWD_A, y.k == 0, CoFwdA<0>, fa)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 5, CoBwdA<5>, ba, RAAE_CO_FWD_B, y.k == 0, CoFwdB<0>, fb)
+    RAAE_CO(plain, RAAE_CO_BWD_B_WGRAD, x.k == 4 && x.kw == 5, CoBwdBW<4 COMMA 5>, bw, RAAE_CO_FWD_A, y.k == 1, CoFwdA<1>, fa)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 4, CoBwdA<4>, ba, RAAE_CO_FWD_B, y.k == 1, CoFwdB<1>, fb)
+    RAAE_CO(plain, RAAE_CO_BWD_B_WGRAD, x.k == 3 && x.kw == 4, CoBwdBW<3 COMMA 4>, bw, RAAE_CO_FWD_A, y.k == 2, CoFwdA<2>, fa)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 3, CoBwdA<3>, ba, RAAE_CO_FWD_B, y.k == 2, CoFwdB<2>, fb)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 2, CoBwdA<2>, ba, RAAE_CO_ADAM, y.wide && y.chk, CoAdam<true>, ad)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 2, CoBwdA<2>, ba, RAAE_CO_ADAM, y.wide && !y.chk, CoAdam<false>, ad)
+    RAAE_CO(plain, RAAE_CO_BWD_B_WGRAD, x.k == 1 && x.kw == 2, CoBwdBW<1 COMMA 2>, bw, RAAE_CO_FWD_A, y.k == 3, CoFwdA<3>, fa)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 1, CoBwdA<1>, ba, RAAE_CO_FWD_B, y.k == 3, CoFwdB<3>, fb)
+    RAAE_CO(plain, RAAE_CO_BWD_B_WGRAD, x.k == 0 && x.kw == 1, CoBwdBW<0 COMMA 1>, bw, RAAE_CO_FWD_A, y.k == 4, CoFwdA<4>, fa)
+    RAAE_CO(plain, RAAE_CO_BWD_A, x.k == 0, CoBwdA<0>, ba, RAAE_CO_FWD_B, y.k == 4, CoFwdB<4>, fb)
+    RAAE_CO(plain, RAAE_CO_WGRAD, x.k == 0, CoWgrad<0>, wg, RAAE_CO_FWD_A, y.k == 5, CoFwdA<5>, fa)
+    RAAE_CO(plain, RAAE_CO_ADAM, x.wide && x.chk, CoAdam<true>, ad, RAAE_CO_FWD_B, y.k == 5, CoFwdB<5>, fb)
+    RAAE_CO(plain, RAAE_CO_ADAM, x.wide && !x.chk, CoAdam<false>, ad, RAAE_CO_FWD_B, y.k == 5, CoFwdB<5>, fb)
+    RAAE_CO(plain, RAAE_CO_FWD_A, x.k == 1, CoFwdA<1>, fa, RAAE_CO_HEAD_FWD, y.k == 4, CoHeadFwd<4>, hf)
+    RAAE_CO(entry, RAAE_CO_FWD_A, x.k == 0, CoFwdA<0>, fa, RAAE_CO_FWD_A, y.k == 6, CoFwdA<6>, fa)
+    RAAE_CO(entry, RAAE_CO_FWD_A, x.k == 0, CoFwdA<0>, fa, RAAE_CO_FWD_A, y.k == 3, CoFwdA<3>, fa)
+    RAAE_CO(entry, RAAE_CO_FWD_A, x.k == 1, CoFwdA<1>, fa, RAAE_CO_FWD_A, y.k == 4, CoFwdA<4>, fa)
+    RAAE_CO(entry, RAAE_CO_FWD_A, x.k == 2, CoFwdA<2>, fa, RAAE_CO_FWD_A, y.k == 5, CoFwdA<5>, fa)
+    RAAE_CO(entry, RAAE_CO_FWD_B, x.k == 0, CoFwdB<0>, fb, RAAE_CO_FWD_B, y.k == 6, CoFwdB<6>, fb)
+    RAAE_CO(entry, RAAE_CO_FWD_B, x.k == 0, CoFwdB<0>, fb, RAAE_CO_FWD_B, y.k == 3, CoFwdB<3>, fb)
+    RAAE_CO(entry, RAAE_CO_FWD_B, x.k == 1, CoFwdB<1>, fb, RAAE_CO_FWD_B, y.k == 4, CoFwdB<4>, fb)
+    RAAE_CO(entry, RAAE_CO_FWD_B, x.k == 2, CoFwdB<2>, fb, RAAE_CO_FWD_B, y.k == 5, CoFwdB<5>, fb)
+    RAAE_CO(entry, kCoBwdB, x.k == 0, CoBwdB<0>, bb, RAAE_CO_WGRAD, y.k == 1, CoWgrad<1>, wg)
+    RAAE_CO(entry, kCoBwdB, x.k == 1, CoBwdB<1>, bb, RAAE_CO_WGRAD, y.k == 2, CoWgrad<2>, wg)
+    RAAE_CO(entry, kCoBwdB, x.k == 3, CoBwdB<3>, bb, RAAE_CO_WGRAD, y.k == 4, CoWgrad<4>, wg)
+    RAAE_CO(entry, kCoBwdB, x.k == 4, CoBwdB<4>, bb, RAAE_CO_WGRAD, y.k == 5, CoWgrad<5>, wg)
+    RAAE_CO(entry, kCoBwdB, x.k == 5, CoBwdB<5>, bb, RAAE_CO_WGRAD, y.k == 6, CoWgrad<6>, wg)
+    RAAE_CO(entry, kCoBwdB, x.k == 2, CoBwdB<2>, bb, RAAE_CO_WGRAD, y.k == 3, CoWgrad<3>, wg)
+    RAAE_CO(entry, kCoBwdB, x.k == 6, CoBwdB<6>, bb, RAAE_CO_WGRAD, y.k == 0, CoWgrad<0>, wg)
+    RAAE_CO(entry, kCoBwdB, x.k == 6, CoBwdB<6>, bb, RAAE_CO_WGRAD, y.k == -1, CoWgrad<-1>, wg)
+    RAAE_CO(entry, kCoBwdB, true, CoBwdB<-1>, bb, RAAE_CO_WGRAD, true, CoWgrad<-1>, wg)
 #undef RAAE_CO
     return 0;
+}
+#undef COMMA
+
+// both sides prepared: one launch where the pair has an instance, else each side's own, x first
+static int co_run(const CoSide& x, const CoSide& y, hipStream_t st, bool entry) {
+    if (co_pair(x, y, st, false, entry)) RAAE_LAUNCH_RET();
+    const int rc = co_single(x, st);
+    return rc ? rc : co_single(y, st);
+}
+// the body of an entry point that launches one side
+static int co_one(int kind, const void* args, int* nparts, void* stream) {
+    static thread_local CoSide s;           // large; per-thread host scratch, filled per call
+    const int rc = co_prep(kind, args, nparts, s);
+    return rc ? rc : co_single(s, (hipStream_t)stream);
+}
+// ... and of one that launches two: the counts are written once both sides have passed their checks
+static int co_two(int kind_x, const void* args_x, int kind_y, const void* args_y, int* nparts_x, int* nparts_y, void* stream) {
+    static thread_local CoSide x, y;
+    int nx = 0, ny = 0;
+    int rc = co_prep(kind_x, args_x, &nx, x);
+    if (rc) return rc;
+    rc = co_prep(kind_y, args_y, &ny, y);
+    if (rc) return rc;
+    if (nparts_x) *nparts_x = nx;
+    if (nparts_y) *nparts_y = ny;
+    return co_run(x, y, (hipStream_t)stream, true);
+}
+
+extern "C" int raae_block_fwd_a(const raae_block_fwd_a_t* in, int* nparts, void* stream) {
+    return co_one(RAAE_CO_FWD_A, in, nparts, stream);
+}
+extern "C" int raae_block_fwd_b(const raae_block_fwd_b_t* in, int* nparts, void* stream) {
+    return co_one(RAAE_CO_FWD_B, in, nparts, stream);
+}
+extern "C" int raae_block_bwd_b(const raae_block_bwd_b_t* in, int* nparts, void* stream) {
+    return co_one(kCoBwdB, in, nparts, stream);
+}
+extern "C" int raae_block_bwd_a(const raae_block_bwd_a_t* in, int* nparts, void* stream) {
+    return co_one(RAAE_CO_BWD_A, in, nparts, stream);
+}
+extern "C" int raae_block_wgrad(const raae_block_wgrad_t* in, int* nslab, void* stream) {
+    const raae_co_wgrad_t p = {in, nslab};
+    return co_one(RAAE_CO_WGRAD, &p, nullptr, stream);
+}
+extern "C" int raae_block_fwd_a2(const raae_block_fwd_a_t* x, const raae_block_fwd_a_t* y, int* nparts_x, int* nparts_y,
+                                 void* stream) {
+    return co_two(RAAE_CO_FWD_A, x, RAAE_CO_FWD_A, y, nparts_x, nparts_y, stream);
+}
+extern "C" int raae_block_fwd_b2(const raae_block_fwd_b_t* x, const raae_block_fwd_b_t* y, int* nparts_x, int* nparts_y,
+                                 void* stream) {
+    return co_two(RAAE_CO_FWD_B, x, RAAE_CO_FWD_B, y, nparts_x, nparts_y, stream);
+}
+extern "C" int raae_block_bwd_b_wgrad(const raae_block_bwd_b_t* bin, const raae_block_wgrad_t* win, int* nparts,
+                                      int* nslab, void* stream) {
+    const raae_co_wgrad_t w = {win, nslab};
+    return co_two(kCoBwdB, bin, RAAE_CO_WGRAD, &w, nparts, nullptr, stream);
 }
 
 extern "C" int raae_co_launch(int kind_x, const void* args_x, int kind_y, const void* args_y, int* nparts_x,
                               int* nparts_y, void* stream) {
     static thread_local CoSide x, y;
-    RAAE_CHECK_ARG(kind_x != RAAE_CO_HEAD_FWD);
+    RAAE_CHECK_ARG(co_public(kind_x) && co_public(kind_y) && kind_x != RAAE_CO_HEAD_FWD);
     int rc = co_prep(kind_x, args_x, nparts_x, x);
     if (rc) return rc;
     rc = co_prep(kind_y, args_y, nparts_y, y);
     if (rc) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    if (co_pair(x, y, st, false)) RAAE_LAUNCH_RET();
-    rc = co_single(x, st);
-    if (rc) return rc;
-    return co_single(y, st);
+    return co_run(x, y, (hipStream_t)stream, false);
 }
 
 extern "C" int raae_co_instance(int kind_x, const void* args_x, int kind_y, const void* args_y) {
     static thread_local CoSide x, y;
+    RAAE_CHECK_ARG(co_public(kind_x) && co_public(kind_y));
     int rc = co_prep(kind_x, args_x, nullptr, x);
     if (rc) return rc < 0 ? rc : -rc;
     rc = co_prep(kind_y, args_y, nullptr, y);
     if (rc) return rc < 0 ? rc : -rc;
-    return co_pair(x, y, nullptr, true);
+    return co_pair(x, y, nullptr, true, false);
 }
-#undef COMMA

@@ -13,6 +13,8 @@ workspace object that carries the attributes ``CompactNet.alloc`` sets; no ``Ste
   block.  In backward the reference takes the kernel's PReLU side only where its own pre-activation lies within 1e-5
   of that tensor's largest magnitude (the band of ``test_disc_fused_matches_autograd``); a sign disagreement
   outside the band fails, the number of entries inside is printed.
+* THE PAIR TABLE (``co_pair`` of csrc/raae_conv.hip, behind every two-body launch): which pairs are one launch at
+  which row counts, as the library answers (``raae_co_instance``) and as the recorder counts the launches.
 * SELF-CONSISTENCY, bit for bit: ``raae_block_fwd_a2`` / ``_b2`` against the two single calls, and
   ``raae_block_bwd_b_wgrad`` against ``raae_block_bwd_b`` followed by ``raae_block_wgrad``.  The ``_m``
   (trial-batched) forms stay with the trial-batch suites (``test_trial_batch_large_gpu.py`` and the trial-mode tests
@@ -39,7 +41,9 @@ cancelling sums) may instead lie within 3x the distance of fp32 CPU autograd of 
 float64 reference, plus the same absolute floor -- the arbiter rule of ``test_p2_teacher_forced_steps``.
 """
 import copy
+import ctypes as C
 import functools
+import os
 import types
 
 import numpy as np
@@ -74,6 +78,13 @@ def _reference(name, rows, gy_bn, masked, seed=0):
     if rows >= BIG_ROWS:
         g32 = br.module_autograd(m, x, g, mask, gy_bn=gy_bn, dtype=torch.float32)[3]
     return m, Lin, x, mask, g, f, b, g32
+
+
+def _inputs(name, rows, masked, seed=0):
+    """The same block and inputs without the reference's forward and backward (tests that compare launches only)."""
+    m, Lin = br.make_block(name, seed)
+    x, mask, g = br.make_inputs(m, Lin, rows, seed)
+    return m, Lin, x, mask if masked else None, g, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------- comparisons
@@ -156,9 +167,10 @@ def _r(t):
 class Rig:
     """One block on the device: module, static description, workspace, gradient slabs and the five launches."""
 
-    def __init__(self, name, rows, gy_bn=False, need_dx=True, masked=True, off=0, seed=0):
+    def __init__(self, name, rows, gy_bn=False, need_dx=True, masked=True, off=0, seed=0, reference=True):
         self.name, self.B, self.gy_bn, self.need_dx, self.off = name, rows, gy_bn, need_dx, off
-        (self.m, self.Lin, self.x, self.mask, self.g, self.f, self.b, self.g32) = _reference(name, rows, gy_bn, masked, seed)
+        (self.m, self.Lin, self.x, self.mask, self.g, self.f, self.b, self.g32) = (
+            _reference(name, rows, gy_bn, masked, seed) if reference else _inputs(name, rows, masked, seed))
         self.md = copy.deepcopy(self.m).to(DEV)
         self.k = k = nets_conv.Block(self.md, self.Lin)
         self.excit, self.short, self.bn1 = k.cve is not None, k.cvs is not None, self.md.bn1 is not None
@@ -728,3 +740,164 @@ def test_bwd_b_wgrad_is_bitwise_the_two_launches(phase_b, tasks, rows):
         res.append((nB, list(ns), dict(r.snapshot(outs), slabs=r.slabs.clone(), slabs_next=nxt.slabs.clone())))
     assert res[0][:2] == res[1][:2]
     _same(res[0][2], res[1][2], f"{phase_b} + {tasks}")
+
+
+# ---------------------------------------------------------------------------------------------- the pair table
+def _ready(name, rows):
+    """A block whose argument blocks pass the host checks without a launch: two statistic rows everywhere."""
+    r = Rig(name, rows, reference=False)
+    r.w.nT1 = r.w.nE2 = r.w.nY = r.w.nB = 2
+    return r
+
+
+def _adam_item(max_nslab, chk, n=256):
+    """What the engine yields for an Adam update that may ride (``StepEngine``: a launch with ``co_args``)."""
+    z = lambda *s, dt=torch.float32: torch.zeros(*s, dtype=dt, device=DEV)
+    keep = [z(n), z(n), z(n), z(max_nslab, n), torch.ones(n // 64, dtype=torch.int16, device=DEV),
+            z(8, dt=torch.float64), z(1, dt=torch.int32), z(1, dt=torch.int32) if chk else None]
+    p, m, v, g, seg, hyper, step, nan = keep
+    return types.SimpleNamespace(co_args=ops.adam_part_args(p, m, v, g, n, seg, n, _lib.OPT_ADAM, hyper, step, max_nslab,
+                                                            nan), keep=keep)
+
+
+def _head_item(rows, C_=4, L=256):
+    """The decoder's head on a [rows, C_, L] tensor behind a BatchNorm (``CompactNet.forward_steps``)."""
+    X, P = torch.zeros(rows, C_, L, device=DEV), torch.zeros(MAXP, C_, 2, dtype=torch.float64, device=DEV)
+    rm, rv = torch.zeros(C_, device=DEV), torch.ones(C_, device=DEV)
+    w, b, out = torch.zeros(1, C_, 1, device=DEV), torch.zeros(1, device=DEV), torch.zeros(rows, 1, L, device=DEV)
+    view = ops.make_view(X, None, ops.make_bn(P, 2, rows * L, rm, rv, 0.1, 1e-5, False))
+    item = ops.conv_fwd_item(view, rows, ops.make_conv(C_, L, 1, L, 1, 1, 0, 0, 1, 0), w, b, out, 1)
+    item.keep = (item.keep, X, P, rm, rv, w, b, out)
+    return item
+
+
+def _side(spec, rows, rigs):
+    """(kind, argument block) as a generator of launches yields it, from a row of ``CO_TABLE``; ``rigs``: one block per
+    shape name, shared by the rows (nothing is launched)."""
+    kind, what = spec[0], spec[1:]
+    if kind == "adam":
+        return kind, _adam_item(*what)
+    if kind == "head":
+        return kind, _head_item(rows, *what)
+    for name in what:
+        if name not in rigs:
+            rigs[name] = _ready(name, rows)
+    r = rigs[what[0]]
+    if kind == "bwd_b":
+        a = r.args_bwd_b(wgrad=rigs[what[1]].args_wgrad())
+    else:
+        a = {"a": r.args_fwd_a, "b": r.args_fwd_b, "bwd_a": r.args_bwd_a, "wgrad": r.args_wgrad}[kind]()
+    return kind, a
+
+
+WIDE, NARROW = 40, 16          # max_nslab of an Adam update: above 16 the wide kernel, which has a body in co_kernel
+# (x, y, one launch at 256 rows, one launch at 1027 rows) -- the answers of raae_co_instance, read off the build BEFORE
+# the forward pairs and bwd_b + wgrad moved into the same table, not off the code under test.  The first 18 are the
+# table's rows for the phase boundaries of the 256-row step; each applies where neither body would run a large-batch
+# (BIG) instance alone, so four of them also hold at 1027 rows: bwd_a of enc1 / enc2 / dec0 and fwd_b of enc2 / dec0 run
+# their plain instance at every row count (kBigMask), and an Adam update has no large-batch form.
+CO_TABLE = [
+    (("bwd_a", "dec3"), ("adam", WIDE, True), 1, 0),
+    (("bwd_a", "dec3"), ("adam", WIDE, False), 1, 0),
+    (("bwd_b", "dec2", "dec3"), ("a", "enc0"), 1, 0),
+    (("bwd_a", "dec2"), ("b", "enc0"), 1, 0),
+    (("bwd_b", "dec1", "dec2"), ("a", "enc1"), 1, 0),
+    (("bwd_a", "dec1"), ("b", "enc1"), 1, 0),
+    (("bwd_b", "dec0", "dec1"), ("a", "enc2"), 1, 0),
+    (("bwd_a", "dec0"), ("b", "enc2"), 1, 1),
+    (("bwd_a", "enc2"), ("adam", WIDE, True), 1, 1),
+    (("bwd_a", "enc2"), ("adam", WIDE, False), 1, 1),
+    (("bwd_b", "enc1", "enc2"), ("a", "dec0"), 1, 0),
+    (("bwd_a", "enc1"), ("b", "dec0"), 1, 1),
+    (("bwd_b", "enc0", "enc1"), ("a", "dec1"), 1, 0),
+    (("bwd_a", "enc0"), ("b", "dec1"), 1, 0),
+    (("wgrad", "enc0"), ("a", "dec2"), 1, 0),
+    (("adam", WIDE, True), ("b", "dec2"), 1, 0),
+    (("adam", WIDE, False), ("b", "dec2"), 1, 0),
+    (("a", "enc1"), ("head", 4), 1, 0),
+    # pairs without a row
+    (("bwd_a", "enc1"), ("b", "dec1"), 0, 0),
+    (("bwd_a", "dec3"), ("adam", NARROW, True), 0, 0),
+    (("bwd_a", "dec2"), ("a", "enc0"), 0, 0),
+    (("bwd_b", "dec2", "dec3"), ("a", "enc1"), 0, 0),
+    (("bwd_b", "dec3", "dec2"), ("a", "enc0"), 0, 0),
+    (("wgrad", "enc1"), ("a", "dec2"), 0, 0),
+    (("a", "enc1"), ("head", 8), 0, 0),
+    (("a", "enc0"), ("head", 4), 0, 0),
+    (("bwd_a", "gen_d"), ("adam", WIDE, False), 0, 0),
+    # the forward pairs' rows belong to raae_block_fwd_a2 / _b2 alone: raae_co_launch runs such a pair as two launches
+    (("a", "enc0"), ("a", "dec3"), 0, 0),
+    (("a", "enc1"), ("b", "dec1"), 0, 0),
+]
+
+
+@pytest.mark.parametrize("rows,col", [(256, 2), (1027, 3)])
+def test_pair_table_answers(rows, col):
+    """``ops.co_pairable`` (``raae_co_instance``) for every row of the cross-phase table and for pairs without one.
+    The answers at 1027 rows are those of the default ``kBigMask``; the ``RAAE_BIG_MASK_*`` tuning overrides, read once
+    when the library loads, would move them, so the test insists that none is set."""
+    assert not [k for k in os.environ if k.startswith("RAAE_BIG_MASK_")], "RAAE_BIG_MASK_* overrides are set"
+    got, rigs = [], {}
+    for row in CO_TABLE:
+        (kx, ax), (ky, ay) = _side(row[0], rows, rigs), _side(row[1], rows, rigs)
+        got.append(int(ops.co_pairable(kx, ax, ky, ay)))
+        print(f"PAIR {rows} rows: {row[0]} + {row[1]}: {got[-1]} (expected {row[col]})")
+    assert got == [row[col] for row in CO_TABLE]
+
+
+def _launches(fn):
+    """How many launches ``fn()`` makes, read through the recorder (as ``TrialBatch`` uses it)."""
+    lib = _lib.load()
+    assert lib.raae_record_begin() == 0
+    try:
+        fn()
+    finally:
+        h, n = C.c_void_p(), C.c_int(0)
+        rc = lib.raae_record_end(C.byref(h), C.byref(n))
+    assert rc == 0
+    lib.raae_record_free(h)
+    torch.cuda.synchronize()
+    return n.value
+
+
+def _launched(name, rows, *launches):
+    """A block without a reference (only launches are counted) after the named launches."""
+    r = Rig(name, rows, reference=False)
+    for step in launches:
+        getattr(r, step)()
+    return r
+
+
+@pytest.mark.parametrize("first,second,rows,want", [("enc0", "dec0", 37, 1), ("enc0", "dec0", 1027, 1),
+                                                    ("enc1", "gen_c", 37, 2)])
+def test_fwd_pair_launch_counts(first, second, rows, want):
+    """``raae_block_fwd_a2`` / ``_b2``: a pair with a row of the table is ONE launch at every row count (the row is not
+    gated by the large-batch instances: it runs the plain bodies), a pair without one is two."""
+    x, y = _launched(first, rows, "fwd_a"), _launched(second, rows, "fwd_a")
+    na = _launches(lambda: ops.block_fwd_pair("a", x.args_fwd_a(), y.args_fwd_a()))
+    nb = _launches(lambda: ops.block_fwd_pair("b", x.args_fwd_b(), y.args_fwd_b()))
+    print(f"LAUNCHES fwd pair {first} + {second} at {rows} rows: a {na}, b {nb} (expected {want})")
+    assert (na, nb) == (want, want)
+
+
+@pytest.mark.parametrize("phase_b,tasks", [("enc0", "enc1"), ("gen_c", "gen_b")])
+@pytest.mark.parametrize("rows", [37, 1027])
+def test_bwd_b_wgrad_launch_counts(phase_b, tasks, rows):
+    """``raae_block_bwd_b_wgrad`` is ONE launch for a table pair and for any other pair (the generic instance), below
+    and above 1024 rows."""
+    nxt = _launched(tasks, rows, "fwd_a", "fwd_b", "bwd_b", "bwd_a")
+    r = _launched(phase_b, rows, "fwd_a", "fwd_b")
+    a = r.args_bwd_b(wgrad=nxt.args_wgrad())
+    n = _launches(lambda: ops.block_bwd_b_launch(a))
+    print(f"LAUNCHES bwd_b {phase_b} + wgrad {tasks} at {rows} rows: {n} (expected 1)")
+    assert n == 1
+
+
+def test_co_launch_without_an_instance_is_two_launches():
+    """``raae_co_launch`` of a pair the table has no row for: the two bodies' own launches, x first."""
+    x, y = _launched("enc1", 37, "fwd_a", "fwd_b", "bwd_b"), _launched("dec1", 37, "fwd_a")
+    ax, ay = x.args_bwd_a(), y.args_fwd_b()
+    assert not ops.co_pairable("bwd_a", ax, "b", ay)
+    n = _launches(lambda: ops.co_launch("bwd_a", ax, "b", ay))
+    print(f"LAUNCHES co_launch bwd_a enc1 + fwd_b dec1: {n} (expected 2)")
+    assert n == 2
