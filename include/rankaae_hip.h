@@ -160,6 +160,17 @@ long raae_rank_loss_work_bytes(int B, int n_aux);
 int raae_rank_loss_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
                            void* work, float* loss, float* dz, void* stream);
 
+/* The same loss on a batch with MISSING labels (ABI 24): a descriptor cell that is not finite (NaN) takes its row out
+ * of that descriptor's pairs.  With S_k the rows labelled for descriptor k and m_k their number,
+ *   loss = -(1 / n_aux) sum_k [ sum_{i,j in S_k} w_k(i,j) (z_ik - z_jk) sign(d_ik - d_jk) ] / max(m_k^2 - m_k, 1),
+ * w_k as above with its pair counts taken inside S_k; a descriptor with m_k < 2 contributes 0; dz[i][k] is a zero for
+ * every i outside S_k and is never NaN; with every cell labelled this is raae_rank_loss_fwd_bwd's formula.  Same single
+ * pass over the pair tiles, no atomics, and the batched (gridDim.z) form.
+ *   work: >= raae_rank_loss_masked_work_bytes(B, n_aux) bytes. */
+long raae_rank_loss_masked_work_bytes(int B, int n_aux);
+int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
+                                  void* work, float* loss, float* dz, void* stream);
+
 /* The same loss over the GLOBAL pairs of a data-parallel batch (what sc/utils/functions.py:63-77 computes on the
  * whole batch in one process), split per rank: this rank owns rows [row0, row0 + nrows) of the all-gathered
  * d_all / z_all [n_all][ld] and pairs them with all n_all rows.
@@ -207,6 +218,16 @@ long raae_select_work_bytes(int n, int k, int n_aux, int n_thresh);
 int raae_select_scores(const float* styles, int n, int k, const double* aux, int n_aux, const float* spec_in,
                        const float* spec_out, int L, const double* thresh, int n_thresh, void* work, double* out,
                        void* stream);
+
+/* raae_select_scores on descriptors with MISSING labels (ABI 24; a cell that is not finite): the scores of descriptor i
+ * -- Spearman, both fits, and for the coordination number the sweeps, the confusion matrix and the F1 -- are formed over
+ * the rows labelled for i alone; fewer than 3 such rows leave the descriptor's slice all zeros (the host reads that as
+ * a missing descriptor).  out[0..3] use all rows and are bitwise raae_select_scores'.  Same layout, same batched form.
+ * work: raae_select_masked_work_bytes(n, k, n_aux, n_thresh) bytes. */
+long raae_select_masked_work_bytes(int n, int k, int n_aux, int n_thresh);
+int raae_select_scores_masked(const float* styles, int n, int k, const double* aux, int n_aux, const float* spec_in,
+                              const float* spec_out, int L, const double* thresh, int n_thresh, void* work, double* out,
+                              void* stream);
 
 /* The adversarial branch of a step in ONE launch (DiscriminatorFC with three layers of width `hidden` = 64 and
  * nstyle <= 16; sc/clustering/model.py:631-663, sc/utils/functions.py:109-132, model.py:8-22): input = [z_real ;
@@ -599,7 +620,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 23
+#define RAAE_ABI_VERSION 24
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -119,10 +119,17 @@ struct RankWork {   // per-workgroup partial: [k]{n_pos, n_neg} ints and {S_pos,
 // reference's loss over one batch; nrows < n_all is one rank's share of the global pairs under data parallelism.
 struct RankPairsArgs { const float* d; int ldd; const float* z; int ldz; int n_all; int row0; int nrows; int nj; int jchunk;
                        RankWork* part; float* gpos; float* gneg; };
-template <int KA, int R>
+// A descriptor cell that is not finite (NaN: no label) takes its row out of that descriptor's pairs.  The test reads the
+// exponent bits: a comparison such as x != x is the compiler's to fold away under -ffinite-math-only.
+__device__ __forceinline__ bool rank_labelled(float d) { return (__float_as_uint(d) & 0x7f800000u) != 0x7f800000u; }
+// MASKED (raae_rank_loss_masked_fwd_bwd): a pair counts only where both its descriptors are labelled -- one test per
+// operand, the j side's once per LDS read, the i side's once per row group -- and labelled[wg][k] receives how many
+// labelled rows of descriptor k the workgroup owns (column block 0 only: every row once).  MASKED = false is the
+// reference's loss, instruction for instruction what it was before the masked form existed.
+template <int KA, int R, bool MASKED>
 __device__ __forceinline__ void rank_pairs_body(const float* d, int ldd, const float* z, int ldz, int n_all,
                                                 int row0, int nrows, int nj, int jchunk,
-                                                RankWork* part, float* gpos, float* gneg) {
+                                                RankWork* part, float* gpos, float* gneg, int* labelled = nullptr) {
     constexpr int IPB = 32 / KA;            // (row, k) slots per block = IPB * KA <= 32
     __shared__ float sd[RANK_TJ * KA], sz[RANK_TJ * KA];
     __shared__ double red_s[2][32];
@@ -132,6 +139,7 @@ __device__ __forceinline__ void rank_pairs_body(const float* d, int ldd, const f
     const bool slot = il < IPB;
     double tsp = 0.0, tsn = 0.0;            // block totals of this (il, k) slot over all its row groups
     long long tnp = 0, tnn = 0;
+    int tlab = 0;
     const int rows_per_group = IPB * R;
     const int ngroups = (nrows + rows_per_group - 1) / rows_per_group;
     const int jb = blockIdx.x % nj, ib = blockIdx.x / nj, ni_wg = gridDim.x / nj;
@@ -139,6 +147,7 @@ __device__ __forceinline__ void rank_pairs_body(const float* d, int ldd, const f
     for (int grp = ib; grp < ngroups; grp += ni_wg) {
         float di[R], zi[R], gp[R], gn[R], sp[R], sn[R];
         int np[R], nn[R], irow[R];
+        bool vi[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             irow[r] = grp * rows_per_group + r * IPB + il;           // local row index
@@ -146,6 +155,11 @@ __device__ __forceinline__ void rank_pairs_body(const float* d, int ldd, const f
             di[r] = ok ? d[(size_t)(row0 + irow[r]) * ldd + k] : 0.f;
             zi[r] = ok ? z[(size_t)(row0 + irow[r]) * ldz + k] : 0.f;
             gp[r] = gn[r] = sp[r] = sn[r] = 0.f; np[r] = nn[r] = 0;
+            vi[r] = true;
+            if constexpr (MASKED) {
+                vi[r] = rank_labelled(di[r]);
+                if (ok && vi[r] && c == 0 && jb == 0) ++tlab;
+            }
         }
         for (int j0 = jlo; j0 < jhi; j0 += RANK_TJ) {
             const int ntile = min(RANK_TJ, jhi - j0);
@@ -159,10 +173,13 @@ __device__ __forceinline__ void rank_pairs_body(const float* d, int ldd, const f
             if (slot) {
                 for (int jj = c; jj < ntile; jj += RANK_JC) {
                     const float dj = sd[jj * KA + k], zj = sz[jj * KA + k];
+                    bool vj = true;
+                    if constexpr (MASKED) vj = rank_labelled(dj);
 #pragma unroll
                     for (int r = 0; r < R; ++r) {
                         const float dd = di[r] - dj;
-                        const float sg = dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f);
+                        float sg = dd > 0.f ? 1.f : (dd < 0.f ? -1.f : 0.f);
+                        if constexpr (MASKED) sg = (vi[r] && vj) ? sg : 0.f;
                         const float p = (zi[r] - zj) * sg;
                         if (p > 0.f) { np[r]++; sp[r] += p; gp[r] += sg; }
                         else if (p < 0.f) { nn[r]++; sn[r] += p; gn[r] += sg; }
@@ -202,16 +219,39 @@ __device__ __forceinline__ void rank_pairs_body(const float* d, int ldd, const f
         part[blockIdx.x].s_pos[tid] = a; part[blockIdx.x].s_neg[tid] = b2;
         part[blockIdx.x].n_pos[tid] = g; part[blockIdx.x].n_neg[tid] = h;
     }
+    if constexpr (MASKED) {
+        __shared__ int red_l[32];
+        if (c == 0) red_l[q] = tlab;
+        __syncthreads();
+        if (tid < KA) {
+            int m = 0;
+            for (int i2 = 0; i2 < IPB; ++i2) m += red_l[i2 * KA + tid];
+            labelled[(size_t)blockIdx.x * RANK_MAXK + tid] = m;
+        }
+    }
 }
 
 template <int KA, int R>
 __global__ __launch_bounds__(256) void rank_pairs_kernel(RankPairsArgs a) {
-    rank_pairs_body<KA, R>(a.d, a.ldd, a.z, a.ldz, a.n_all, a.row0, a.nrows, a.nj, a.jchunk, a.part, a.gpos, a.gneg);
+    rank_pairs_body<KA, R, false>(a.d, a.ldd, a.z, a.ldz, a.n_all, a.row0, a.nrows, a.nj, a.jchunk, a.part, a.gpos, a.gneg);
 }
 template <int KA, int R>
 __global__ __launch_bounds__(256) void rank_pairs_kernel_m(const RankPairsArgs* t) {
     const RankPairsArgs a = t[blockIdx.z];
-    rank_pairs_body<KA, R>(a.d, a.ldd, a.z, a.ldz, a.n_all, a.row0, a.nrows, a.nj, a.jchunk, a.part, a.gpos, a.gneg);
+    rank_pairs_body<KA, R, false>(a.d, a.ldd, a.z, a.ldz, a.n_all, a.row0, a.nrows, a.nj, a.jchunk, a.part, a.gpos, a.gneg);
+}
+
+struct RankMaskedPairsArgs { RankPairsArgs p; int* labelled; };
+template <int KA, int R>
+__global__ __launch_bounds__(256) void rank_pairs_masked_kernel(RankMaskedPairsArgs a) {
+    rank_pairs_body<KA, R, true>(a.p.d, a.p.ldd, a.p.z, a.p.ldz, a.p.n_all, a.p.row0, a.p.nrows, a.p.nj, a.p.jchunk,
+                                 a.p.part, a.p.gpos, a.p.gneg, a.labelled);
+}
+template <int KA, int R>
+__global__ __launch_bounds__(256) void rank_pairs_masked_kernel_m(const RankMaskedPairsArgs* t) {
+    const RankMaskedPairsArgs a = t[blockIdx.z];
+    rank_pairs_body<KA, R, true>(a.p.d, a.p.ldd, a.p.z, a.p.ldz, a.p.n_all, a.p.row0, a.p.nrows, a.p.nj, a.p.jchunk,
+                                 a.p.part, a.p.gpos, a.p.gneg, a.labelled);
 }
 
 // finalize: c_k, loss, dz[i][k] = -(2/norm)(c_k g+ + g-).  Every workgroup re-derives c_k from the
@@ -294,6 +334,77 @@ __global__ __launch_bounds__(256) void rank_finalize_kernel(RankFinArgs a) {
 __global__ __launch_bounds__(256) void rank_finalize_kernel_m(const RankFinArgs* t) {
     const RankFinArgs a = t[blockIdx.z];
     rank_finalize_body(a.part, a.nparts, a.totals, a.n_all, a.nrows, a.nj, a.KA, a.activate, a.scale, a.gpos, a.gneg, a.loss, a.dz, a.ldz);
+}
+
+// finalize of the masked form: descriptor k is normalised by ITS labelled pairs, norm_k = max(m_k^2 - m_k, 1), m_k the
+// sum of the workgroups' labelled-row counts (integers: exact), and the n_aux terms are averaged:
+//   loss = -(1 / KA) sum_k (c_k S+_k + S-_k) / norm_k,  dz[i][k] = -(2 / (KA norm_k)) (c_k g+ + g-).
+// A row without a label for k has g+ = g- = 0, so its dz is a zero; m_k < 2 has no pair, so S+- = 0 and the term is 0.
+// With every cell labelled m_k = B for all k: the reference's (B^2 - B) KA.
+struct RankMaskedFinArgs { const RankWork* part; const int* labelled; int nparts; int nrows; int nj; int KA; int activate;
+                           const float* gpos; const float* gneg; float* loss; float* dz; int ldz; };
+__device__ __forceinline__ void rank_masked_finalize_body(const RankMaskedFinArgs& a) {
+    __shared__ float s_c[RANK_MAXK], s_f[RANK_MAXK];
+    __shared__ double s_loss[RANK_MAXK];
+    __shared__ double r_s[2][256];
+    __shared__ long long r_n[3][256];
+    const int tid = threadIdx.x, KA = a.KA;
+    {
+        const int k = tid & 15, sl = tid >> 4;          // 16 slices
+        long long np = 0, nn = 0, m = 0; double sp = 0.0, sn = 0.0;
+        if (k < KA) {
+#pragma unroll 8
+            for (int p = sl; p < a.nparts; p += 16) {
+                np += a.part[p].n_pos[k]; nn += a.part[p].n_neg[k];
+                sp += a.part[p].s_pos[k]; sn += a.part[p].s_neg[k];
+                m += a.labelled[(size_t)p * RANK_MAXK + k];
+            }
+        }
+        r_s[0][tid] = sp; r_s[1][tid] = sn; r_n[0][tid] = np; r_n[1][tid] = nn; r_n[2][tid] = m;
+    }
+    __syncthreads();
+    if (tid < KA) {
+        long long np = 0, nn = 0, m = 0; double sp = 0.0, sn = 0.0;
+        for (int sl = 0; sl < 16; ++sl) {
+            sp += r_s[0][sl * 16 + tid]; sn += r_s[1][sl * 16 + tid];
+            np += r_n[0][sl * 16 + tid]; nn += r_n[1][sl * 16 + tid]; m += r_n[2][sl * 16 + tid];
+        }
+        double c = 1.0;
+        if (a.activate) {
+            const double n_same = (double)(np > 1 ? np : 1), n_opp = (double)(nn > 1 ? nn : 1);
+            c = n_opp / (n_same > n_opp ? n_same : n_opp);
+        }
+        const double pairs = (double)m * (double)m - (double)m;
+        const double norm = (pairs > 1.0 ? pairs : 1.0) * (double)KA;
+        s_c[tid] = (float)c;
+        s_f[tid] = (float)(-2.0 / norm);
+        s_loss[tid] = (c * sp + sn) / norm;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) {
+        double t = 0.0;
+        for (int k = 0; k < KA; ++k) t += s_loss[k];
+        a.loss[0] = (float)(-t);
+    }
+    if (a.dz != nullptr) {
+        const long n = (long)a.nrows * a.ldz;
+        const size_t blk = (size_t)a.nrows * KA;
+        for (long idx = (long)blockIdx.x * 256 + tid; idx < n; idx += (long)gridDim.x * 256) {
+            const int i = (int)(idx / a.ldz), k = (int)(idx - (long)i * a.ldz);
+            float v = 0.f;
+            if (k < KA) {
+                float gp = 0.f, gn = 0.f;
+                for (int b = 0; b < a.nj; ++b) { gp += a.gpos[b * blk + (size_t)i * KA + k]; gn += a.gneg[b * blk + (size_t)i * KA + k]; }
+                v = s_f[k] * (s_c[k] * gp + gn);
+            }
+            a.dz[idx] = v;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void rank_masked_finalize_kernel(RankMaskedFinArgs a) { rank_masked_finalize_body(a); }
+__global__ __launch_bounds__(256) void rank_masked_finalize_kernel_m(const RankMaskedFinArgs* t) {
+    const RankMaskedFinArgs a = t[blockIdx.z];
+    rank_masked_finalize_body(a);
 }
 
 // per-descriptor totals {n+, n-, S+, S-} of this rank's pairs as [4][16] doubles (fixed order): what a data-parallel
@@ -663,6 +774,40 @@ extern "C" int raae_rank_loss_fwd_bwd(const float* d, int ldd, const float* z, i
     const int gf = dz ? grid_for((long)B * ldz, 256, 256) : 1;
     const RankFinArgs fa = {(const RankWork*)work, g.nwg, (const double*)nullptr, B, B, g.nj, n_aux, activate, 1.f, gpos, gneg, loss, dz, ldz};
     raae::launch(rank_finalize_kernel, rank_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
+    RAAE_LAUNCH_RET();
+}
+
+// The rank loss on a batch with unlabelled cells (a descriptor that is not finite): same pair pass, same grid, plus the
+// labelled-row counts [RANK_MAXWG][16] ints behind the gradient partials of the work buffer.
+static size_t rank_grad_bytes(int B, int n_aux) { return (2 * (size_t)RANK_MAXNJ * B * n_aux * sizeof(float) + 255) & ~(size_t)255; }
+extern "C" long raae_rank_loss_masked_work_bytes(int B, int n_aux) {
+    return (long)(rank_part_bytes() + rank_grad_bytes(B, n_aux) + (size_t)RANK_MAXWG * RANK_MAXK * sizeof(int) + 256);
+}
+
+extern "C" int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
+                                             void* work, float* loss, float* dz, void* stream) {
+    RAAE_CHECK_ARG(d && z && work && loss && B > 1 && n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
+    hipStream_t st = (hipStream_t)stream;
+    const RankGrid g = rank_grid(B, B, n_aux);
+    float* gpos = (float*)((char*)work + rank_part_bytes());
+    float* gneg = gpos + (size_t)RANK_MAXNJ * B * n_aux;
+    int* labelled = (int*)((char*)work + rank_part_bytes() + rank_grad_bytes(B, n_aux));
+    const RankMaskedPairsArgs pa = {{d, ldd, z, ldz, B, 0, B, g.nj, g.jchunk, (RankWork*)work, gpos, gneg}, labelled};
+#define RANK_CASE(KA) case KA: \
+        if (g.R == 1) raae::launch(rank_pairs_masked_kernel<KA, 1>, rank_pairs_masked_kernel_m<KA, 1>, dim3(g.nwg), dim3(256), 0, st, pa); \
+        else raae::launch(rank_pairs_masked_kernel<KA, 4>, rank_pairs_masked_kernel_m<KA, 4>, dim3(g.nwg), dim3(256), 0, st, pa); \
+        break;
+    switch (n_aux) {
+        RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
+        RANK_CASE(9) RANK_CASE(10) RANK_CASE(11) RANK_CASE(12) RANK_CASE(13) RANK_CASE(14) RANK_CASE(15) RANK_CASE(16)
+        default: return RAAE_EINVAL;
+    }
+#undef RANK_CASE
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    const int gf = dz ? grid_for((long)B * ldz, 256, 256) : 1;
+    const RankMaskedFinArgs fa = {(const RankWork*)work, labelled, g.nwg, B, g.nj, n_aux, activate, gpos, gneg, loss, dz, ldz};
+    raae::launch(rank_masked_finalize_kernel, rank_masked_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
     RAAE_LAUNCH_RET();
 }
 

@@ -16,6 +16,12 @@
 // Counts are integers; every floating sum is double, strided per thread, then a wave64 shuffle tree, then the four
 // wave totals in order: no atomics, so a replay is bitwise repeatable.  Inputs are taken to be finite (the reference
 // masks NaN rows out before its statistics; a model that produces NaN styles has no place in a ranking).
+//
+// raae_select_scores_masked: a descriptor cell that is not finite (NaN) is a missing label.  The same four bodies are
+// instantiated a second time on SelArgsM; there every per-descriptor score of descriptor i is formed over S_i, the rows
+// whose cell i is labelled (m_i of them; fewer than 3: the slice is zeros), which takes the average ranks of style i
+// among the rows of S_i (rank_zs, n_aux more columns of the rank kernel).  The head of the block uses all rows and is
+// bitwise what raae_select_scores writes.
 #include "raae_common.h"
 
 namespace {
@@ -27,6 +33,11 @@ struct SelArgs {
     double* rank_z; double* rank_d; double* mae; int* sweep; double* out;
     int n, k, n_aux, L, n_th;
 };
+struct SelArgsM : SelArgs { double* rank_zs; };      // [n_aux][n]: ranks of style i among the rows labelled for descriptor i
+template <class A> constexpr bool kMasked = false;
+template <> constexpr bool kMasked<SelArgsM> = true;
+// the exponent bits, not x == x: the test must hold under -ffinite-math-only too
+__device__ __forceinline__ bool labelled(double x) { return (__double2hiint(x) & 0x7ff00000) != 0x7ff00000; }
 
 // ---- block-wide reductions (256 threads = 4 waves); the result is valid in every thread --------------------------------
 template <int NV>
@@ -67,14 +78,26 @@ __device__ __forceinline__ double block_min(double v, double* sh) {
 }
 
 // ---- ranks: grid (ceil(n / 256), k + n_aux); column c < k is style c, column k + i is descriptor i ----------------------
-__device__ __forceinline__ void sel_rank_body(const SelArgs& a) {
+template <class A>
+__device__ __forceinline__ void sel_rank_body(const A& a) {
     __shared__ __attribute__((aligned(16))) double tile[kTile];
-    const int c = blockIdx.y, tid = threadIdx.x, n = a.n;
-    if (c == a.k + 1) return;                            // the coordination number is classified, never ranked
+    int c = blockIdx.y;
+    const int tid = threadIdx.x, n = a.n;
+    // masked form, columns k + n_aux + i: style i among the rows labelled for descriptor i
+    const bool sub = kMasked<A> && c >= a.k + a.n_aux;
+    const int dsub = c - a.k - a.n_aux;
+    if (sub) c = dsub;
+    if (sub ? dsub == 1 : c == a.k + 1) return;          // the coordination number is classified, never ranked
     const bool st = c < a.k;
     const int ld = st ? a.k : a.n_aux, col = st ? c : c - a.k;
     auto at = [&](int j) -> double {
-        return st ? (double)a.z[(size_t)j * ld + col] : a.aux[(size_t)j * ld + col];
+        const double v = st ? (double)a.z[(size_t)j * ld + col] : a.aux[(size_t)j * ld + col];
+        if constexpr (kMasked<A>) {
+            // an unlabelled row stands at +infinity: below no one, equal to no labelled value.  (Its own rank is never read.)
+            const double lab = sub ? a.aux[(size_t)j * a.n_aux + dsub] : (st ? 0.0 : v);
+            if (!labelled(lab)) return __builtin_huge_val();
+        }
+        return v;
     };
     const int i = blockIdx.x * 256 + tid;
     const double xi = i < n ? at(i) : 0.0;
@@ -98,12 +121,14 @@ __device__ __forceinline__ void sel_rank_body(const SelArgs& a) {
     }
     if (i < n) {
         double* rank = st ? a.rank_z + (size_t)c * n : a.rank_d + (size_t)col * n;
+        if constexpr (kMasked<A>) { if (sub) rank = a.rank_zs + (size_t)dsub * n; }
         rank[i] = (double)less + 0.5 * (double)(eq + 1);
     }
 }
 
 // ---- MAE of each spectrum: grid (ceil(n / 4)), one wave per row (sklearn: mean |y_pred - y_true|, fp32 difference) -----
-__device__ __forceinline__ void sel_mae_body(const SelArgs& a) {
+template <class A>
+__device__ __forceinline__ void sel_mae_body(const A& a) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= a.n) return;
     const float* x = a.sin + (size_t)row * a.L;
@@ -119,13 +144,15 @@ __device__ __forceinline__ double cn_class(double cn) { return trunc(cn - 4.0); 
 
 // ---- threshold sweeps: grid (n_th, 2).  sweep[s][t] = {2 TP, 2 TP + FP + FN}: F1 is their quotient, 0 where the
 // denominator is 0 (zero_division=0) --------------------------------------------------------------------------------------
-__device__ __forceinline__ void sel_sweep_body(const SelArgs& a) {
+template <class A>
+__device__ __forceinline__ void sel_sweep_body(const A& a) {
     __shared__ int sh[12];
     const int t = blockIdx.x, s = blockIdx.y, n = a.n;
     const double th = a.th[t];
     int c[3] = {0, 0, 0};                                // TP, predicted positives, actual positives
     for (int i = threadIdx.x; i < n; i += 256) {
         const double z = (double)a.z[(size_t)i * a.k + 1];        // numpy promotes the fp32 style to the float64 threshold
+        if constexpr (kMasked<A>) { if (!labelled(a.aux[(size_t)i * a.n_aux + 1])) continue; }
         const double cls = cn_class(a.aux[(size_t)i * a.n_aux + 1]);
         const int p = s == 0 ? z < th : z > th;
         const int q = s == 0 ? cls < 1.0 : cls > 1.0;
@@ -167,11 +194,12 @@ __device__ __forceinline__ int sweep_argmax(const SelArgs& a, int s, int* sh) {
     return best;
 }
 
-__device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
+template <class A>
+__device__ __forceinline__ void sel_stat_body(const A& a) {
     __shared__ double shd[13 * 4];
     __shared__ int shi[3 * 256];
     const int tid = threadIdx.x, w = blockIdx.x, n = a.n, k = a.k;
-    const double dn = (double)n;
+    double dn = (double)n;
     if (w == 0) {
         // Reconstruct Err: np.mean / np.std (population) of the per-spectrum MAEs
         double s[1] = {0.0};
@@ -184,7 +212,7 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
         if (tid == 0) { a.out[0] = mean; a.out[1] = sqrt(q[0] / dn); a.out[3] = 0.0; }
         return;
     }
-    const double rmean = 0.5 * (dn + 1.0);               // average ranks always sum to n (n + 1) / 2
+    double rmean = 0.5 * (dn + 1.0);                     // average ranks always sum to n (n + 1) / 2
     if (w == 1) {
         // Inter-style Corr: max_i |spearman(style_i, style_{k-1})|, i < k - 1 (analysis.py:321-325)
         const double* rl = a.rank_z + (size_t)(k - 1) * n;
@@ -206,6 +234,23 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
     }
     const int d = w - 2;
     double* o = a.out + RAAE_SEL_HEAD + (size_t)RAAE_SEL_STRIDE * d;
+    // masked form: row i takes part iff its cell of descriptor d is labelled; dn becomes the number of such rows
+    auto V = [&](int i) -> bool {
+        if constexpr (kMasked<A>) return labelled(a.aux[(size_t)i * a.n_aux + d]);
+        return true;
+    };
+    if constexpr (kMasked<A>) {
+        int m[1] = {0};
+        for (int i = tid; i < n; i += 256) m[0] += V(i);
+        block_sum<1>(m, shi);
+        __syncthreads();                                 // shi is reused below
+        if (m[0] < 3) {                                  // uniform: no score from fewer than three labelled rows
+            for (int u = tid; u < RAAE_SEL_STRIDE; u += 256) o[u] = 0.0;
+            return;
+        }
+        dn = (double)m[0];
+        rmean = 0.5 * (dn + 1.0);
+    }
     if (d == 1) {
         // coordination number (get_confusion_matrix, analysis.py:234-269)
         for (int u = tid; u < RAAE_SEL_STRIDE; u += 256) o[u] = 0.0;
@@ -216,6 +261,7 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
         for (int pass = 0; pass < 4; ++pass) {
             double m = inf;
             for (int i = tid; i < n; i += 256) {
+                if (!V(i)) continue;
                 const double c = cn_class(a.aux[(size_t)i * a.n_aux + 1]);
                 if (c > floor_) m = fmin(m, c);
             }
@@ -233,6 +279,7 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
 #pragma unroll
         for (int u = 0; u < 12; ++u) c[u] = 0;
         for (int i = tid; i < n; i += 256) {
+            if (!V(i)) continue;
             const double z = (double)a.z[(size_t)i * k + 1];
             const double cls = cn_class(a.aux[(size_t)i * a.n_aux + 1]);
             const int p = (z > t45) + (z > t56);
@@ -266,12 +313,14 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
     // get_descriptor_style_correlation as evaluate_model calls it: x = descriptor, y = style (analysis.py:445)
     const double* rx = a.rank_d + (size_t)d * n;
     const double* ry = a.rank_z + (size_t)d * n;
+    if constexpr (kMasked<A>) ry = a.rank_zs + (size_t)d * n;
     auto X = [&](int i) -> double { return a.aux[(size_t)i * a.n_aux + d]; };
     auto Y = [&](int i) -> double { return (double)a.z[(size_t)i * k + d]; };
     double s[2] = {0.0, 0.0};
     const double inf = __builtin_huge_val();
     double lo = inf, nhi = inf;
     for (int i = tid; i < n; i += 256) {
+        if (!V(i)) continue;
         const double x = X(i);
         s[0] += x; s[1] += Y(i);
         lo = fmin(lo, x); nhi = fmin(nhi, -x);
@@ -286,6 +335,7 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
 #pragma unroll
     for (int u = 0; u < 13; ++u) t[u] = 0.0;
     for (int i = tid; i < n; i += 256) {
+        if (!V(i)) continue;
         const double x = X(i), y = Y(i), dx = x - xm, dy = y - ym;
         t[0] += dx * dx; t[1] += dx * dy; t[2] += dy * dy;
         const double p = rx[i] - rmean, q = ry[i] - rmean;
@@ -308,6 +358,7 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
     const double a2 = b2 / m22, a1 = (b1 - m12 * a2) / m11, a0 = (b0 - m01 * a1 - m02 * a2) / m00;
     double e[2] = {0.0, 0.0};
     for (int i = tid; i < n; i += 256) {
+        if (!V(i)) continue;
         const double u = off + scl * X(i), f = a0 + u * (a1 + u * a2), r = Y(i) - f;
         e[0] += f; e[1] += r * r;
     }
@@ -315,6 +366,7 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
     const double fm = e[0] / dn;
     double g[2] = {0.0, 0.0};
     for (int i = tid; i < n; i += 256) {
+        if (!V(i)) continue;
         const double u = off + scl * X(i), df = a0 + u * (a1 + u * a2) - fm;
         g[0] += df * df; g[1] += df * (Y(i) - ym);
     }
@@ -336,16 +388,22 @@ __device__ __forceinline__ void sel_stat_body(const SelArgs& a) {
     }
 }
 
-#define SEL_KERNEL_PAIR(NAME)                                                                                    \
-    __global__ __launch_bounds__(256) void NAME##_kernel(SelArgs a) { NAME##_body(a); }                          \
-    __global__ __launch_bounds__(256) void NAME##_kernel_m(const SelArgs* t) {     /* one model per grid plane */ \
-        const SelArgs a = t[blockIdx.z];                                                                         \
+#define SEL_KERNEL_PAIR(NAME, ARGS)                                                                              \
+    __global__ __launch_bounds__(256) void NAME##_kernel(ARGS a) { NAME##_body(a); }                             \
+    __global__ __launch_bounds__(256) void NAME##_kernel_m(const ARGS* t) {        /* one model per grid plane */ \
+        const ARGS a = t[blockIdx.z];                                                                            \
         NAME##_body(a);                                                                                          \
     }
-SEL_KERNEL_PAIR(sel_rank)
-SEL_KERNEL_PAIR(sel_mae)
-SEL_KERNEL_PAIR(sel_sweep)
-SEL_KERNEL_PAIR(sel_stat)
+#define sel_rank_masked_body sel_rank_body
+#define sel_sweep_masked_body sel_sweep_body
+#define sel_stat_masked_body sel_stat_body
+SEL_KERNEL_PAIR(sel_rank, SelArgs)
+SEL_KERNEL_PAIR(sel_mae, SelArgs)
+SEL_KERNEL_PAIR(sel_sweep, SelArgs)
+SEL_KERNEL_PAIR(sel_stat, SelArgs)
+SEL_KERNEL_PAIR(sel_rank_masked, SelArgsM)
+SEL_KERNEL_PAIR(sel_sweep_masked, SelArgsM)
+SEL_KERNEL_PAIR(sel_stat_masked, SelArgsM)
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
@@ -356,6 +414,18 @@ extern "C" long raae_select_work_bytes(int n, int k, int n_aux, int n_thresh) {
     return (long)(align256(sizeof(double) * (size_t)n * (size_t)(k + n_aux + 1)) + align256(sizeof(int) * 4 * (size_t)n_thresh));
 }
 
+// `extra`: rank columns behind the k + n_aux + 1 the unmasked form uses
+static void sel_fill(SelArgs& a, const float* styles, int n, int k, const double* aux, int n_aux, const float* spec_in,
+                     const float* spec_out, int L, const double* thresh, int n_thresh, void* work, double* out, int extra) {
+    a.z = styles; a.aux = aux; a.sin = spec_in; a.sout = spec_out; a.th = thresh;
+    a.rank_z = (double*)work;
+    a.rank_d = a.rank_z + (size_t)k * n;
+    a.mae = a.rank_d + (size_t)n_aux * n;
+    a.sweep = (int*)((char*)work + align256(sizeof(double) * (size_t)n * (size_t)(k + n_aux + 1 + extra)));
+    a.out = out;
+    a.n = n; a.k = k; a.n_aux = n_aux; a.L = L; a.n_th = n_thresh;
+}
+
 extern "C" int raae_select_scores(const float* styles, int n, int k, const double* aux, int n_aux, const float* spec_in,
                                   const float* spec_out, int L, const double* thresh, int n_thresh, void* work,
                                   double* out, void* stream) {
@@ -363,18 +433,35 @@ extern "C" int raae_select_scores(const float* styles, int n, int k, const doubl
     RAAE_CHECK_ARG(n >= 3 && k >= 2 && k <= 64 && n_aux >= 1 && n_aux <= k && L >= 1);
     RAAE_CHECK_ARG(n_aux < 2 || (thresh && n_thresh >= 1 && n_thresh <= 65535));
     SelArgs a;
-    a.z = styles; a.aux = aux; a.sin = spec_in; a.sout = spec_out; a.th = thresh;
-    a.rank_z = (double*)work;
-    a.rank_d = a.rank_z + (size_t)k * n;
-    a.mae = a.rank_d + (size_t)n_aux * n;
-    a.sweep = (int*)((char*)work + align256(sizeof(double) * (size_t)n * (size_t)(k + n_aux + 1)));
-    a.out = out;
-    a.n = n; a.k = k; a.n_aux = n_aux; a.L = L; a.n_th = n_thresh;
+    sel_fill(a, styles, n, k, aux, n_aux, spec_in, spec_out, L, thresh, n_thresh, work, out, 0);
     const hipStream_t st = (hipStream_t)stream;
     raae::launch(sel_rank_kernel, sel_rank_kernel_m, dim3(raae::cdiv(n, 256), k + n_aux), dim3(256), 0, st, a);
     raae::launch(sel_mae_kernel, sel_mae_kernel_m, dim3(raae::cdiv(n, 4)), dim3(256), 0, st, a);
     if (n_aux >= 2)
         raae::launch(sel_sweep_kernel, sel_sweep_kernel_m, dim3(n_thresh, 2), dim3(256), 0, st, a);
     raae::launch(sel_stat_kernel, sel_stat_kernel_m, dim3(2 + n_aux), dim3(256), 0, st, a);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" long raae_select_masked_work_bytes(int n, int k, int n_aux, int n_thresh) {
+    if (n < 1 || k < 1 || n_aux < 0 || n_thresh < 0) return -1;
+    return (long)(align256(sizeof(double) * (size_t)n * (size_t)(k + 2 * n_aux + 1)) + align256(sizeof(int) * 4 * (size_t)n_thresh));
+}
+
+extern "C" int raae_select_scores_masked(const float* styles, int n, int k, const double* aux, int n_aux, const float* spec_in,
+                                         const float* spec_out, int L, const double* thresh, int n_thresh, void* work,
+                                         double* out, void* stream) {
+    RAAE_CHECK_ARG(styles && aux && spec_in && spec_out && work && out);
+    RAAE_CHECK_ARG(n >= 3 && k >= 2 && k <= 64 && n_aux >= 1 && n_aux <= k && L >= 1);
+    RAAE_CHECK_ARG(n_aux < 2 || (thresh && n_thresh >= 1 && n_thresh <= 65535));
+    SelArgsM a;
+    sel_fill(a, styles, n, k, aux, n_aux, spec_in, spec_out, L, thresh, n_thresh, work, out, n_aux);
+    a.rank_zs = a.mae + n;
+    const hipStream_t st = (hipStream_t)stream;
+    raae::launch(sel_rank_masked_kernel, sel_rank_masked_kernel_m, dim3(raae::cdiv(n, 256), k + 2 * n_aux), dim3(256), 0, st, a);
+    raae::launch(sel_mae_kernel, sel_mae_kernel_m, dim3(raae::cdiv(n, 4)), dim3(256), 0, st, (const SelArgs&)a);
+    if (n_aux >= 2)
+        raae::launch(sel_sweep_masked_kernel, sel_sweep_masked_kernel_m, dim3(n_thresh, 2), dim3(256), 0, st, a);
+    raae::launch(sel_stat_masked_kernel, sel_stat_masked_kernel_m, dim3(2 + n_aux), dim3(256), 0, st, a);
     RAAE_LAUNCH_RET();
 }

@@ -1,6 +1,6 @@
 """Dataset ingest with the reference's semantics (``sc/clustering/dataloader.py:8-77``):
 CSV with two index columns, ``n_aux`` ``AUX_*`` columns then ``ENE_<eV>`` columns; contiguous
-70/15/15 row split; float64 -> float32; training rows reshuffled every epoch; the last,
+70/15/15 row split; float64 -> float32; an empty AUX cell is NaN, a missing label; training rows reshuffled every epoch; the last,
 partial batch is kept.  Unlike the reference the CSV is parsed ONCE and the split arrays go
 to the device whole -- batches are gathered there by index (``raae_gather_batch``)."""
 import numpy as np
@@ -68,7 +68,13 @@ def _parse_csv(csv_fn, n_aux):
         assert "AUX_" in cols[0]
         assert "AUX_" in cols[n_aux - 1]
     grid = np.array([float(c.strip("ENE_")) for c in cols if c.startswith("ENE_")])
-    data = df.to_numpy()
+    # an empty (or "NaN") AUX cell is a missing label and stays NaN; a spectrum has to be complete
+    data = df.to_numpy(dtype=np.float64)
+    bad = np.argwhere(~np.isfinite(data[:, n_aux:]))
+    if len(bad):
+        r, c = bad[0]
+        raise ValueError(f"{csv_fn}: spectrum value of row {df.index[r]} (data row {r}), column {cols[n_aux + c]} is "
+                         f"empty or not finite ({len(bad)} such cells); only AUX_* cells may be missing")
     return data[:, n_aux:], (data[:, :n_aux] if n_aux > 0 else None), grid, df.index.to_list()
 
 

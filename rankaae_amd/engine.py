@@ -540,6 +540,9 @@ class StepEngine:
         # rank loss under data parallelism: "local" = pairs inside each rank's shard (DDP semantics, no exchange);
         # "global" = all pairs of the global batch, i.e. the reference's loss on that batch (functions.py:63-77)
         self.rank_pairs_global = self.world_size > 1 and str(cfg.get("rank_loss_pairs", "local")) == "global"
+        # whether the data holds NaN descriptor cells, i.e. missing labels (set_data): the rank loss then runs its masked
+        # form, in training and validation alike; without any, exactly the kernels of fully labelled data
+        self.aux_missing = False
         self.L = cfg["dim_in"]
         self._make_optimizers()
         self.steps_dev = torch.zeros(8, dtype=torch.int32, device=device)
@@ -699,7 +702,16 @@ class StepEngine:
             self.bn_counts[id(bn)] = self.bn_counts.get(id(bn), 0) + 1
 
     @_on_stream
-    def set_data(self, train_spec, train_aux):
+    def set_data(self, train_spec, train_aux, aux_missing=None):
+        """``aux_missing``: whether ANY split of the data (the validation rows too) holds a NaN descriptor cell;
+        None: decided from ``train_aux`` alone.  Decided here, once, before the first step plan exists."""
+        if aux_missing is None:
+            aux_missing = bool(torch.isnan(torch.as_tensor(train_aux)).any())
+        if aux_missing and self.rank_pairs_global:
+            raise ValueError("rank_loss_pairs: global is not implemented for data with missing descriptors (NaN AUX "
+                             "cells): use rank_loss_pairs: local")
+        assert not self.plans or aux_missing == self.aux_missing, "set_data after the first step changed aux_missing"
+        self.aux_missing = bool(aux_missing)
         self.train_spec = torch.as_tensor(train_spec, dtype=torch.float32).contiguous().to(self.device)
         self.train_aux = torch.as_tensor(train_aux, dtype=torch.float32).contiguous().to(self.device)
         self.perm = torch.arange(len(self.train_spec), dtype=torch.int64, device=self.device)
@@ -837,7 +849,7 @@ class StepEngine:
         P.m_enc.append(self.enc.mask_slots(tape, b))            # phase E :191
         P.m_dec.append(self.dec.mask_slots(tape, b))
         tape.finalize(dev)
-        P.rank_work = torch.empty(ops.rank_loss_work_bytes(b, self.n_aux), dtype=torch.uint8, device=dev)
+        P.rank_work = torch.empty(self._rank_work_bytes(b), dtype=torch.uint8, device=dev)
         if self.rank_pairs_global:
             P.aux_all = torch.empty(self.world_size * b, self.n_aux, device=dev)
             P.z_all = torch.empty(self.world_size * b, ns, device=dev)
@@ -962,12 +974,19 @@ class StepEngine:
         else:
             self._cut(lambda: self._run_comm(kind, bufs))
 
+    def _rank_work_bytes(self, rows):
+        return (ops.rank_loss_masked_work_bytes if self.aux_missing else ops.rank_loss_work_bytes)(rows, self.n_aux)
+
     def _rank_loss(self, P, styles):
         """Phase B's loss and d(loss)/d(styles).  Data parallel with ``rank_loss_pairs: global``: the ranks exchange
         their [b, n_aux] descriptors and styles (all-gather), every rank pairs ITS rows with all W*b rows, the
         per-descriptor pair counts and sums meet in one 512-byte all-reduce, and the row-local gradient is exact;
         it is scaled by W because the parameter gradients are averaged over the ranks afterwards."""
         c, b, ns, lo = self.cfg, P.b, self.nstyle, self.loss_out
+        if self.aux_missing:        # rows without a label for descriptor k leave its pairs (never with global pairs: set_data)
+            ops.rank_loss_masked_fwd_bwd(P.aux, self.n_aux, styles, ns, b, self.n_aux, c["kendall_activation"],
+                                         P.rank_work, lo[1:2], P.dstyles)
+            return
         if not self.rank_pairs_global:
             ops.rank_loss_fwd_bwd(P.aux, self.n_aux, styles, ns, b, self.n_aux, c["kendall_activation"], P.rank_work,
                                   lo[1:2], P.dstyles)
@@ -1381,7 +1400,8 @@ class StepEngine:
         # and raae_rank_rows_finish forms the loss, identical on every rank and equal to the replicated computation to
         # the order of the float64 sums (47 ms -> 47 / W ms at n_val = 150 k).  The O(n_val) parts (forwards, the four
         # other losses, the style metrics, which need every row's styles) stay replicated.
-        shard = self.world_size > 1 and bool(c.get("shard_validation", True))
+        # (missing labels: the masked rank loss has no rows-against-all form; every rank computes it whole)
+        shard = self.world_size > 1 and bool(c.get("shard_validation", True)) and not self.aux_missing
         if key not in self.plans:
             V = StepPlan()
             V.enc, V.dec = self.enc.alloc(nv), self.dec.alloc(nv)
@@ -1392,7 +1412,7 @@ class StepEngine:
             V.tape.draw("normal", V.z_sample, (nv, ns))
             V.sl_disc = self.disc.tape_slots(V.tape, bc, nv, train=False)
             V.tape.finalize(dev)
-            V.rank_work = torch.empty(ops.rank_loss_work_bytes(nv, self.n_aux), dtype=torch.uint8, device=dev)
+            V.rank_work = torch.empty(self._rank_work_bytes(nv), dtype=torch.uint8, device=dev)
             V.rank_totals = torch.zeros(64, dtype=torch.float64, device=dev)
             V.lpart = torch.zeros(RAAE_MAX_PARTS, dtype=torch.float64, device=dev)
             V.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -1427,6 +1447,9 @@ class StepEngine:
                 self._collective(V.rank_totals, "sum")
                 ops.rank_rows_finish(V.rank_totals, nv, max(nrows, 1), self.n_aux, c["kendall_activation"], 1.0,
                                      V.rank_work, V.out[1:2], None, ns)
+            elif self.aux_missing:
+                ops.rank_loss_masked_fwd_bwd(val_aux, self.n_aux, z, ns, nv, self.n_aux, c["kendall_activation"],
+                                             V.rank_work, V.out[1:2], None)
             else:
                 ops.rank_loss_fwd_bwd(val_aux, self.n_aux, z, ns, nv, self.n_aux, c["kendall_activation"], V.rank_work,
                                       V.out[1:2], None)

@@ -200,6 +200,19 @@ def rank_loss_fwd_bwd(d, ldd, z, ldz, B, n_aux, activate, work, loss, dz):
     _probed("rank_pairs_kernel", 4 * B * n_aux * 3, launch)      # O(B) bytes for B^2 n_aux pair operations: VALU-bound
 
 
+def rank_loss_masked_work_bytes(B, n_aux):
+    return int(_lib.load().raae_rank_loss_masked_work_bytes(B, n_aux))
+
+
+def rank_loss_masked_fwd_bwd(d, ldd, z, ldz, B, n_aux, activate, work, loss, dz):
+    """The rank loss where NaN cells of ``d`` are missing labels (``raae_rank_loss_masked_fwd_bwd``)."""
+    def launch():
+        check(_lib.load().raae_rank_loss_masked_fwd_bwd(_ptr(d), ldd, _ptr(z), ldz, B, n_aux, 1 if activate else 0,
+                                                        _ptr(work, None), _ptr(loss), _ptr(dz), _stream()),
+              "raae_rank_loss_masked_fwd_bwd")
+    _probed("rank_pairs_masked_kernel", 4 * B * n_aux * 3, launch)
+
+
 def rank_rows_pairs(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, work, totals):
     check(_lib.load().raae_rank_rows_pairs(_ptr(d_all), ldd, _ptr(z_all), ldz, n_all, row0, nrows, n_aux, _ptr(work, None),
                                            _ptr(totals, torch.float64), _stream()), "raae_rank_rows_pairs")
@@ -220,19 +233,22 @@ def group_mean(x, groups, per, L, out):
     check(_lib.load().raae_group_mean(_ptr(x), groups, per, L, _ptr(out), _stream()), "raae_group_mean")
 
 
-def select_work_bytes(n, k, n_aux, n_thresh):
-    return int(_lib.load().raae_select_work_bytes(n, k, n_aux, n_thresh))
+def select_work_bytes(n, k, n_aux, n_thresh, masked=False):
+    fn = _lib.load().raae_select_masked_work_bytes if masked else _lib.load().raae_select_work_bytes
+    return int(fn(n, k, n_aux, n_thresh))
 
 
-def select_scores(styles, n, k, aux, n_aux, spec_in, spec_out, L, thresh, work, out):
+def select_scores(styles, n, k, aux, n_aux, spec_in, spec_out, L, thresh, work, out, masked=False):
     """Model-selection scores of one model (``raae_select_scores``): ``aux`` and ``thresh`` float64, ``out`` float64
-    ``[SEL_HEAD + SEL_STRIDE * n_aux]``, ``work`` a byte buffer of ``select_work_bytes``."""
+    ``[SEL_HEAD + SEL_STRIDE * n_aux]``, ``work`` a byte buffer of ``select_work_bytes``.  ``masked``: NaN cells of
+    ``aux`` are missing labels (``raae_select_scores_masked``; ``work`` sized with ``masked=True``)."""
     assert out.numel() >= _lib.SEL_HEAD + _lib.SEL_STRIDE * n_aux
-    assert work.numel() * work.element_size() >= select_work_bytes(n, k, n_aux, thresh.numel())
+    assert work.numel() * work.element_size() >= select_work_bytes(n, k, n_aux, thresh.numel(), masked)
     assert styles.numel() == n * k and aux.numel() == n * n_aux and spec_in.numel() == n * L and spec_out.numel() == n * L
-    check(_lib.load().raae_select_scores(_ptr(styles), n, k, _ptr(aux, torch.float64), n_aux, _ptr(spec_in),
-                                         _ptr(spec_out), L, _ptr(thresh, torch.float64), thresh.numel(), _ptr(work, None),
-                                         _ptr(out, torch.float64), _stream()), "raae_select_scores")
+    name = "raae_select_scores_masked" if masked else "raae_select_scores"
+    check(getattr(_lib.load(), name)(_ptr(styles), n, k, _ptr(aux, torch.float64), n_aux, _ptr(spec_in),
+                                     _ptr(spec_out), L, _ptr(thresh, torch.float64), thresh.numel(), _ptr(work, None),
+                                     _ptr(out, torch.float64), _stream()), name)
 
 
 def _fin(fin):

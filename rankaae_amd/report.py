@@ -44,15 +44,17 @@ class SelectionScorer:
     """Device buffers of one model's ``raae_select_scores`` call.  ``launch`` enqueues the four kernels on the current
     stream (capturable, recordable); ``read`` copies the block back."""
 
-    def __init__(self, n, k, n_aux, L, device):
+    def __init__(self, n, k, n_aux, L, device, masked=False):
         self.n, self.k, self.n_aux, self.L = int(n), int(k), int(n_aux), int(L)
+        self.masked = bool(masked)        # some descriptor cells are NaN (missing labels): the masked kernels
         self.thresh = torch.tensor(THRESH_GRID, dtype=torch.float64, device=device)
-        self.work = torch.empty(ops.select_work_bytes(n, k, n_aux, self.thresh.numel()), dtype=torch.uint8, device=device)
+        self.work = torch.empty(ops.select_work_bytes(n, k, n_aux, self.thresh.numel(), self.masked), dtype=torch.uint8,
+                                device=device)
         self.out = torch.zeros(SEL_HEAD + SEL_STRIDE * n_aux, dtype=torch.float64, device=device)
 
     def launch(self, styles, aux, spec_in, spec_out):
         ops.select_scores(styles, self.n, self.k, aux, self.n_aux, spec_in, spec_out, self.L, self.thresh, self.work,
-                          self.out)
+                          self.out, masked=self.masked)
 
     def read(self):
         return self.out.cpu().numpy()
@@ -62,16 +64,30 @@ def _r4(x):
     return np.round(float(x), 4).tolist()
 
 
-def result_from_block(block, n_aux):
+def has_missing(*aux):
+    """Whether any descriptor cell of the given arrays is NaN, i.e. a missing label (None entries are skipped).  Asked
+    once, where the data is loaded: the answer picks the masked kernels for the whole run."""
+    return any(a is not None and bool(np.isnan(np.asarray(a)).any()) for a in aux)
+
+
+def labelled_counts(aux):
+    """Labelled (non-NaN) rows per descriptor column."""
+    return (~np.isnan(np.asarray(aux, dtype=np.float64))).sum(axis=0)
+
+
+def result_from_block(block, n_aux, labelled=None):
     """The reference's result dict (without ``Input`` / ``Output``) from one model's block of doubles, rounded where and
     how ``analysis.py`` rounds: Python ``round`` for the reconstruction error, the F1 score, the thresholds and the
     inter-style correlation, ``np.round`` for the rest; ``residue`` is a one-element list, as ``np.round`` of lstsq's
-    residual array gives it."""
+    residual array gives it.  ``labelled``: labelled rows per descriptor (``labelled_counts``); a descriptor with fewer
+    than 3 is ``None``, which ``score_matrix`` scores like a missing descriptor."""
     block = np.asarray(block, dtype=np.float64)
     corr = {}
     for i in range(n_aux):
         o = block[SEL_HEAD + SEL_STRIDE * i:SEL_HEAD + SEL_STRIDE * (i + 1)]
-        if i == 1:
+        if labelled is not None and labelled[i] < 3:
+            corr[i] = None
+        elif i == 1:
             if o[0] == 0.0:
                 corr[i] = None
                 continue
@@ -96,10 +112,10 @@ def _device_inputs(styles, aux, spec_in, spec_out, device):
 
 def score_arrays(styles, aux, spec_in, spec_out, device=None):
     """One model's unrounded block for host arrays ``styles [n, k]``, ``aux [n, n_aux]``, ``spec_in`` / ``spec_out``
-    ``[n, L]`` (single-model launches)."""
+    ``[n, L]`` (single-model launches).  NaN cells of ``aux`` are missing labels."""
     device = device or torch.device("cuda:0")
     z, a, si, so = _device_inputs(styles, aux, spec_in, spec_out, device)
-    sc = SelectionScorer(z.shape[0], z.shape[1], a.shape[1], si.shape[1], device)
+    sc = SelectionScorer(z.shape[0], z.shape[1], a.shape[1], si.shape[1], device, masked=has_missing(aux))
     sc.launch(z, a, si, so)
     return sc.read()
 
@@ -161,7 +177,9 @@ def score_arrays_batched(inputs, device=None):
     ``gridDim.z = J`` launch sequence.  Raises if the recorder refuses (it cannot for these kernels)."""
     device = device or torch.device("cuda:0")
     dev_in = [_device_inputs(*x, device) for x in inputs]
-    scorers = [SelectionScorer(z.shape[0], z.shape[1], a.shape[1], si.shape[1], device) for z, a, si, _ in dev_in]
+    masked = has_missing(*[x[1] for x in inputs])
+    scorers = [SelectionScorer(z.shape[0], z.shape[1], a.shape[1], si.shape[1], device, masked=masked)
+               for z, a, si, _ in dev_in]
     stream = torch.cuda.Stream(device=device)
     stream.wait_stream(torch.cuda.current_stream(device))
     with torch.cuda.stream(stream):
@@ -225,7 +243,9 @@ class _Job:
             R.enc, R.dec = eng.enc.alloc(n), eng.dec.alloc(n)
             eng.plans[key] = R
         self.plan = eng.plans[key]
-        self.scorer = SelectionScorer(n, eng.nstyle, self.n_aux, L, dev)
+        # decided once, from the split that is scored: NaN descriptor cells are missing labels
+        self.labelled = labelled_counts(test_ds.aux) if has_missing(test_ds.aux) else None
+        self.scorer = SelectionScorer(n, eng.nstyle, self.n_aux, L, dev, masked=self.labelled is not None)
         self.z = self.out = None
 
     def emit(self):
@@ -236,7 +256,7 @@ class _Job:
         self.scorer.launch(self.z, self.aux, self.spec, self.out)
 
     def result(self):
-        res = result_from_block(self.scorer.read(), self.n_aux)
+        res = result_from_block(self.scorer.read(), self.n_aux, self.labelled)
         res["Input"] = self.spec.cpu().numpy()
         res["Output"] = self.out.cpu().numpy()
         return res

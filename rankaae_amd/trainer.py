@@ -128,7 +128,16 @@ class Trainer:
         ds = train_loader.dataset
         if ds.aux is None:
             raise ValueError("n_aux: 0 is not reachable in the reference (SURVEY.md finding 4)")
-        self.engine.set_data(ds.spec, ds.aux)
+        # NaN descriptor cells are missing labels.  Decided once, over the training and validation splits together: any
+        # such cell and the run uses the masked rank loss throughout; none and it launches what it always launched
+        splits = [ds.aux, getattr(getattr(val_loader, "dataset", None), "aux", None)]
+        self.aux_missing = any(a is not None and bool(np.isnan(np.asarray(a, dtype=np.float64)).any()) for a in splits)
+        if self.aux_missing:
+            lab = np.concatenate([~np.isnan(np.asarray(a, dtype=np.float64)) for a in splits if a is not None])
+            self.logger.info("Missing descriptors (NaN AUX cells): labelled fraction per descriptor " +
+                             ", ".join(f"AUX_{k}: {f:.4f}" for k, f in enumerate(lab.mean(axis=0))) +
+                             "; the rank loss pairs only rows labelled for a descriptor.")
+        self.engine.set_data(ds.spec, ds.aux, aux_missing=self.aux_missing)
         self.load_optimizers()
         self.load_schedulers()
 
