@@ -179,11 +179,30 @@ int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const float* z, int l
  *   raae_rank_rows_finish: global loss (identical on every rank) and dz [nrows][ldz] = scale * dL/dz of this
  *   rank's rows (exact: every pair that contains row i is seen by its owner); scale = number of ranks when the
  *   parameter gradients are AVERAGED over ranks afterwards.
- *   work: >= raae_rank_loss_work_bytes(nrows, n_aux) bytes, the same buffer for both calls. */
+ *   work: >= raae_rank_loss_work_bytes(nrows, n_aux) bytes, the same buffer for both calls.
+ * Both read every descriptor as a label; a batch with NaN cells takes the masked pair below. */
 int raae_rank_rows_pairs(const float* d_all, int ldd, const float* z_all, int ldz, int n_all, int row0, int nrows,
                          int n_aux, void* work, double* totals, void* stream);
 int raae_rank_rows_finish(const double* totals, int n_all, int nrows, int n_aux, int activate, float scale,
                           void* work, float* loss, float* dz, int ldz, void* stream);
+
+/* The same split of raae_rank_loss_masked_fwd_bwd (ABI 25): the global pairs of a batch with MISSING labels, same
+ * arguments and conventions as the pair above.
+ *   raae_rank_rows_masked_pairs:  the masked pair pass of this rank's rows against all n_all rows (a pair counts only
+ *   where both cells are labelled); totals[80] doubles = this rank's {n+[16], n-[16], S+[16], S-[16], m[16]}, m[k] the
+ *   number of THIS rank's rows labelled for descriptor k.  The ranks' rows partition the batch, so the sum of `totals`
+ *   over the ranks -- one 640-byte all-reduce -- holds the global counts (exact in double) and sums.
+ *   raae_rank_rows_masked_finish: from the summed totals, on every rank alike, raae_rank_loss_masked_fwd_bwd's loss on
+ *   the whole batch (norm_k = max(m_k^2 - m_k, 1) n_aux, w_k from the global pair counts, 0 from a descriptor with
+ *   m_k < 2) and dz [nrows][ldz] = scale * dL/dz of this rank's rows: a zero where the row is unlabelled for k and in
+ *   columns >= n_aux, never NaN.  dz == NULL: the loss alone (validation).
+ *   work: >= raae_rank_rows_masked_work_bytes(nrows, n_aux) bytes, the same buffer for both calls.
+ * No atomics, fixed summation order; the totals kernel has no batched (gridDim.z) form, as raae_rank_rows_pairs'. */
+long raae_rank_rows_masked_work_bytes(int nrows, int n_aux);
+int raae_rank_rows_masked_pairs(const float* d_all, int ldd, const float* z_all, int ldz, int n_all, int row0, int nrows,
+                                int n_aux, void* work, double* totals, void* stream);
+int raae_rank_rows_masked_finish(const double* totals, int n_all, int nrows, int n_aux, int activate, float scale,
+                                 void* work, float* loss, float* dz, int ldz, void* stream);
 
 /* Model-selection metrics of the validation styles (sc/clustering/trainer.py:286-292: scipy.stats.shapiro on
  * every style column, scipy.stats.spearmanr on every column pair of the host copy), computed where the styles
@@ -620,7 +639,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 24
+#define RAAE_ABI_VERSION 25
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -434,6 +434,87 @@ __global__ __launch_bounds__(256) void rank_totals_kernel(const RankWork* part, 
     }
 }
 
+// the masked pair pass's totals {n+, n-, S+, S-, m} as [5][16] doubles: rank_totals_kernel's four in its order, and m_k,
+// the labelled rows of descriptor k among THIS rank's rows (the workgroups' counts, integers: exact).  The ranks' rows
+// partition the batch, so the sum over the ranks holds the global m_k beside the global pair counts and sums.
+__global__ __launch_bounds__(256) void rank_masked_totals_kernel(const RankWork* part, const int* labelled, int nparts, int KA,
+                                                                 double* totals) {
+    __shared__ double r_s[2][256];
+    __shared__ long long r_n[3][256];
+    const int tid = threadIdx.x, k = tid & 15, sl = tid >> 4;
+    long long np = 0, nn = 0, m = 0; double sp = 0.0, sn = 0.0;
+    if (k < KA) {
+#pragma unroll 8
+        for (int p = sl; p < nparts; p += 16) {
+            np += part[p].n_pos[k]; nn += part[p].n_neg[k];
+            sp += part[p].s_pos[k]; sn += part[p].s_neg[k];
+            m += labelled[(size_t)p * RANK_MAXK + k];
+        }
+    }
+    r_s[0][tid] = sp; r_s[1][tid] = sn; r_n[0][tid] = np; r_n[1][tid] = nn; r_n[2][tid] = m;
+    __syncthreads();
+    if (tid < 16) {
+        np = 0; nn = 0; m = 0; sp = 0.0; sn = 0.0;
+        if (tid < KA)
+            for (int s2 = 0; s2 < 16; ++s2) {
+                sp += r_s[0][s2 * 16 + tid]; sn += r_s[1][s2 * 16 + tid];
+                np += r_n[0][s2 * 16 + tid]; nn += r_n[1][s2 * 16 + tid]; m += r_n[2][s2 * 16 + tid];
+            }
+        totals[tid] = (double)np; totals[16 + tid] = (double)nn; totals[32 + tid] = sp; totals[48 + tid] = sn;
+        totals[64 + tid] = (double)m;
+    }
+}
+
+// finalize of the masked form from GIVEN totals [5][16] (summed over the ranks of a data-parallel run): the arithmetic of
+// rank_masked_finalize_body with n+-, S+- and m_k read instead of added up, so every rank forms the loss of the whole
+// batch; `scale` multiplies dz as in rank_finalize_body.  dz covers this rank's nrows rows, whose g+- the pair pass left.
+struct RankRowsMaskedFinArgs { const double* totals; int nrows; int nj; int KA; int activate; float scale;
+                               const float* gpos; const float* gneg; float* loss; float* dz; int ldz; };
+__device__ __forceinline__ void rank_rows_masked_finalize_body(const RankRowsMaskedFinArgs& a) {
+    __shared__ float s_c[RANK_MAXK], s_f[RANK_MAXK];
+    __shared__ double s_loss[RANK_MAXK];
+    const int tid = threadIdx.x, KA = a.KA;
+    if (tid < KA) {
+        const long long np = (long long)a.totals[tid], nn = (long long)a.totals[16 + tid];      // exact: counts < 2^53
+        const double sp = a.totals[32 + tid], sn = a.totals[48 + tid], m = a.totals[64 + tid];
+        double c = 1.0;
+        if (a.activate) {
+            const double n_same = (double)(np > 1 ? np : 1), n_opp = (double)(nn > 1 ? nn : 1);
+            c = n_opp / (n_same > n_opp ? n_same : n_opp);
+        }
+        const double pairs = m * m - m;
+        const double norm = (pairs > 1.0 ? pairs : 1.0) * (double)KA;
+        s_c[tid] = (float)c;
+        s_f[tid] = (float)(-2.0 / norm) * a.scale;
+        s_loss[tid] = (c * sp + sn) / norm;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) {
+        double t = 0.0;
+        for (int k = 0; k < KA; ++k) t += s_loss[k];
+        a.loss[0] = (float)(-t);
+    }
+    if (a.dz != nullptr) {
+        const long n = (long)a.nrows * a.ldz;
+        const size_t blk = (size_t)a.nrows * KA;
+        for (long idx = (long)blockIdx.x * 256 + tid; idx < n; idx += (long)gridDim.x * 256) {
+            const int i = (int)(idx / a.ldz), k = (int)(idx - (long)i * a.ldz);
+            float v = 0.f;
+            if (k < KA) {
+                float gp = 0.f, gn = 0.f;
+                for (int b = 0; b < a.nj; ++b) { gp += a.gpos[b * blk + (size_t)i * KA + k]; gn += a.gneg[b * blk + (size_t)i * KA + k]; }
+                v = s_f[k] * (s_c[k] * gp + gn);
+            }
+            a.dz[idx] = v;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void rank_rows_masked_finalize_kernel(RankRowsMaskedFinArgs a) { rank_rows_masked_finalize_body(a); }
+__global__ __launch_bounds__(256) void rank_rows_masked_finalize_kernel_m(const RankRowsMaskedFinArgs* t) {
+    const RankRowsMaskedFinArgs a = t[blockIdx.z];
+    rank_rows_masked_finalize_body(a);
+}
+
 // ------------------------------------------------------------------ reconstruction loss
 // functions.py:81-107.  One wave per row; L <= 1024.
 // Optional finalisation inside the loss kernel: after thread 0 has stored this workgroup's partial, the LAST workgroup
@@ -784,15 +865,14 @@ extern "C" long raae_rank_loss_masked_work_bytes(int B, int n_aux) {
     return (long)(rank_part_bytes() + rank_grad_bytes(B, n_aux) + (size_t)RANK_MAXWG * RANK_MAXK * sizeof(int) + 256);
 }
 
-extern "C" int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
-                                             void* work, float* loss, float* dz, void* stream) {
-    RAAE_CHECK_ARG(d && z && work && loss && B > 1 && n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
-    hipStream_t st = (hipStream_t)stream;
-    const RankGrid g = rank_grid(B, B, n_aux);
-    float* gpos = (float*)((char*)work + rank_part_bytes());
-    float* gneg = gpos + (size_t)RANK_MAXNJ * B * n_aux;
-    int* labelled = (int*)((char*)work + rank_part_bytes() + rank_grad_bytes(B, n_aux));
-    const RankMaskedPairsArgs pa = {{d, ldd, z, ldz, B, 0, B, g.nj, g.jchunk, (RankWork*)work, gpos, gneg}, labelled};
+// the masked pair pass of rows [row0, row0 + nrows) against all n_all rows; the work buffer's layout follows nrows
+static int rank_pairs_masked_launch(const float* d, int ldd, const float* z, int ldz, int n_all, int row0, int nrows, int n_aux,
+                                    void* work, RankGrid& g, float*& gpos, float*& gneg, int*& labelled, hipStream_t st) {
+    g = rank_grid(n_all, nrows, n_aux);
+    gpos = (float*)((char*)work + rank_part_bytes());
+    gneg = gpos + (size_t)RANK_MAXNJ * nrows * n_aux;
+    labelled = (int*)((char*)work + rank_part_bytes() + rank_grad_bytes(nrows, n_aux));
+    const RankMaskedPairsArgs pa = {{d, ldd, z, ldz, n_all, row0, nrows, g.nj, g.jchunk, (RankWork*)work, gpos, gneg}, labelled};
 #define RANK_CASE(KA) case KA: \
         if (g.R == 1) raae::launch(rank_pairs_masked_kernel<KA, 1>, rank_pairs_masked_kernel_m<KA, 1>, dim3(g.nwg), dim3(256), 0, st, pa); \
         else raae::launch(rank_pairs_masked_kernel<KA, 4>, rank_pairs_masked_kernel_m<KA, 4>, dim3(g.nwg), dim3(256), 0, st, pa); \
@@ -803,7 +883,17 @@ extern "C" int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const floa
         default: return RAAE_EINVAL;
     }
 #undef RANK_CASE
-    const int rc = (int)hipGetLastError();
+    return (int)hipGetLastError();
+}
+
+extern "C" int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
+                                             void* work, float* loss, float* dz, void* stream) {
+    RAAE_CHECK_ARG(d && z && work && loss && B > 1 && n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
+    hipStream_t st = (hipStream_t)stream;
+    RankGrid g;
+    float *gpos, *gneg;
+    int* labelled;
+    const int rc = rank_pairs_masked_launch(d, ldd, z, ldz, B, 0, B, n_aux, work, g, gpos, gneg, labelled, st);
     if (rc) return rc;
     const int gf = dz ? grid_for((long)B * ldz, 256, 256) : 1;
     const RankMaskedFinArgs fa = {(const RankWork*)work, labelled, g.nwg, B, g.nj, n_aux, activate, gpos, gneg, loss, dz, ldz};
@@ -837,6 +927,40 @@ extern "C" int raae_rank_rows_finish(const double* totals, int n_all, int nrows,
     const int gf = dz ? grid_for((long)nrows * ldz, 256, 256) : 1;
     const RankFinArgs fa = {(const RankWork*)nullptr, 0, totals, n_all, nrows, g.nj, n_aux, activate, scale, gpos, gneg, loss, dz, ldz};
     raae::launch(rank_finalize_kernel, rank_finalize_kernel_m, dim3(gf), dim3(256), 0, (hipStream_t)stream, fa);
+    RAAE_LAUNCH_RET();
+}
+
+// The rows-against-all pair on a batch with missing labels: the masked pair pass over this rank's rows, its totals with
+// the labelled-row counts m_k as a fifth block (80 doubles: one 640-byte all-reduce), and the masked finalize from the
+// summed totals -- raae_rank_loss_masked_fwd_bwd's loss on the whole batch, on every rank alike.
+extern "C" long raae_rank_rows_masked_work_bytes(int nrows, int n_aux) { return raae_rank_loss_masked_work_bytes(nrows, n_aux); }
+
+extern "C" int raae_rank_rows_masked_pairs(const float* d_all, int ldd, const float* z_all, int ldz, int n_all, int row0,
+                                           int nrows, int n_aux, void* work, double* totals, void* stream) {
+    RAAE_CHECK_ARG(d_all && z_all && work && totals && n_all > 1 && nrows >= 1 && row0 >= 0 && row0 + nrows <= n_all &&
+                   n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
+    hipStream_t st = (hipStream_t)stream;
+    RankGrid g;
+    float *gpos, *gneg;
+    int* labelled;
+    const int rc = rank_pairs_masked_launch(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, work, g, gpos, gneg, labelled, st);
+    if (rc) return rc;
+    RAAE_PLAIN_LAUNCH(rank_masked_totals_kernel, dim3(1), dim3(256), 0, st, (const RankWork*)work, (const int*)labelled, g.nwg,
+                      n_aux, totals);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_rank_rows_masked_finish(const double* totals, int n_all, int nrows, int n_aux, int activate, float scale,
+                                            void* work, float* loss, float* dz, int ldz, void* stream) {
+    RAAE_CHECK_ARG(totals && work && loss && n_all > 1 && nrows >= 1 && nrows <= n_all && n_aux >= 1 && n_aux <= RANK_MAXK &&
+                   (!dz || ldz >= n_aux));
+    const RankGrid g = rank_grid(n_all, nrows, n_aux);
+    float* gpos = (float*)((char*)work + rank_part_bytes());
+    float* gneg = gpos + (size_t)RANK_MAXNJ * nrows * n_aux;
+    const int gf = dz ? grid_for((long)nrows * ldz, 256, 256) : 1;
+    const RankRowsMaskedFinArgs fa = {totals, nrows, g.nj, n_aux, activate, scale, gpos, gneg, loss, dz, ldz};
+    raae::launch(rank_rows_masked_finalize_kernel, rank_rows_masked_finalize_kernel_m, dim3(gf), dim3(256), 0,
+                 (hipStream_t)stream, fa);
     RAAE_LAUNCH_RET();
 }
 

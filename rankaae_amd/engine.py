@@ -707,9 +707,6 @@ class StepEngine:
         None: decided from ``train_aux`` alone.  Decided here, once, before the first step plan exists."""
         if aux_missing is None:
             aux_missing = bool(torch.isnan(torch.as_tensor(train_aux)).any())
-        if aux_missing and self.rank_pairs_global:
-            raise ValueError("rank_loss_pairs: global is not implemented for data with missing descriptors (NaN AUX "
-                             "cells): use rank_loss_pairs: local")
         assert not self.plans or aux_missing == self.aux_missing, "set_data after the first step changed aux_missing"
         self.aux_missing = bool(aux_missing)
         self.train_spec = torch.as_tensor(train_spec, dtype=torch.float32).contiguous().to(self.device)
@@ -849,11 +846,11 @@ class StepEngine:
         P.m_enc.append(self.enc.mask_slots(tape, b))            # phase E :191
         P.m_dec.append(self.dec.mask_slots(tape, b))
         tape.finalize(dev)
-        P.rank_work = torch.empty(self._rank_work_bytes(b), dtype=torch.uint8, device=dev)
+        P.rank_work = torch.empty(self._rank_work_bytes(b, rows_form=self.rank_pairs_global), dtype=torch.uint8, device=dev)
         if self.rank_pairs_global:
             P.aux_all = torch.empty(self.world_size * b, self.n_aux, device=dev)
             P.z_all = torch.empty(self.world_size * b, ns, device=dev)
-            P.rank_totals = torch.zeros(64, dtype=torch.float64, device=dev)
+            P.rank_totals = torch.zeros(80 if self.aux_missing else 64, dtype=torch.float64, device=dev)
         P.dstyles = torch.empty(b, ns, device=dev)
         P.dspec = torch.empty(b, self.L, device=dev)
         P.dout = torch.empty(b, self.L, device=dev)
@@ -974,31 +971,33 @@ class StepEngine:
         else:
             self._cut(lambda: self._run_comm(kind, bufs))
 
-    def _rank_work_bytes(self, rows):
-        return (ops.rank_loss_masked_work_bytes if self.aux_missing else ops.rank_loss_work_bytes)(rows, self.n_aux)
+    def _rank_work_bytes(self, rows, rows_form=False):
+        """``rows_form``: the buffer of a rows-against-all pair over ``rows`` of this rank's rows."""
+        if self.aux_missing:
+            return (ops.rank_rows_masked_work_bytes if rows_form else ops.rank_loss_masked_work_bytes)(rows, self.n_aux)
+        return ops.rank_loss_work_bytes(rows, self.n_aux)
 
     def _rank_loss(self, P, styles):
         """Phase B's loss and d(loss)/d(styles).  Data parallel with ``rank_loss_pairs: global``: the ranks exchange
         their [b, n_aux] descriptors and styles (all-gather), every rank pairs ITS rows with all W*b rows, the
         per-descriptor pair counts and sums meet in one 512-byte all-reduce, and the row-local gradient is exact;
-        it is scaled by W because the parameter gradients are averaged over the ranks afterwards."""
+        it is scaled by W because the parameter gradients are averaged over the ranks afterwards.  Missing labels
+        (``aux_missing``): the masked kernels; with global pairs the all-reduce also carries the per-descriptor
+        labelled-row counts (640 bytes), so every rank normalises by the labelled pairs of the whole batch."""
         c, b, ns, lo = self.cfg, P.b, self.nstyle, self.loss_out
-        if self.aux_missing:        # rows without a label for descriptor k leave its pairs (never with global pairs: set_data)
-            ops.rank_loss_masked_fwd_bwd(P.aux, self.n_aux, styles, ns, b, self.n_aux, c["kendall_activation"],
-                                         P.rank_work, lo[1:2], P.dstyles)
-            return
         if not self.rank_pairs_global:
-            ops.rank_loss_fwd_bwd(P.aux, self.n_aux, styles, ns, b, self.n_aux, c["kendall_activation"], P.rank_work,
-                                  lo[1:2], P.dstyles)
+            # (missing labels: rows without a label for descriptor k leave its pairs)
+            fwd_bwd = ops.rank_loss_masked_fwd_bwd if self.aux_missing else ops.rank_loss_fwd_bwd
+            fwd_bwd(P.aux, self.n_aux, styles, ns, b, self.n_aux, c["kendall_activation"], P.rank_work, lo[1:2], P.dstyles)
             return
         W = self.world_size
+        pairs, finish = ((ops.rank_rows_masked_pairs, ops.rank_rows_masked_finish) if self.aux_missing else
+                         (ops.rank_rows_pairs, ops.rank_rows_finish))
         self._collective(P.aux, "gather", P.aux_all)
         self._collective(styles, "gather", P.z_all)
-        ops.rank_rows_pairs(P.aux_all, self.n_aux, P.z_all, ns, W * b, self.rank * b, b, self.n_aux, P.rank_work,
-                            P.rank_totals)
+        pairs(P.aux_all, self.n_aux, P.z_all, ns, W * b, self.rank * b, b, self.n_aux, P.rank_work, P.rank_totals)
         self._collective(P.rank_totals, "sum")
-        ops.rank_rows_finish(P.rank_totals, W * b, b, self.n_aux, c["kendall_activation"], float(W), P.rank_work,
-                             lo[1:2], P.dstyles, ns)
+        finish(P.rank_totals, W * b, b, self.n_aux, c["kendall_activation"], float(W), P.rank_work, lo[1:2], P.dstyles, ns)
 
     def _begin_phase(self, record):
         self._slab_notes = np.zeros(self.arena.n // 64, dtype=np.int16) if record else None
@@ -1400,8 +1399,10 @@ class StepEngine:
         # and raae_rank_rows_finish forms the loss, identical on every rank and equal to the replicated computation to
         # the order of the float64 sums (47 ms -> 47 / W ms at n_val = 150 k).  The O(n_val) parts (forwards, the four
         # other losses, the style metrics, which need every row's styles) stay replicated.
-        # (missing labels: the masked rank loss has no rows-against-all form; every rank computes it whole)
-        shard = self.world_size > 1 and bool(c.get("shard_validation", True)) and not self.aux_missing
+        # Missing labels: the same split by the masked pair (raae_rank_rows_masked_pairs / _finish), whose all-reduce
+        # also carries the labelled-row counts per descriptor (640 bytes): n_val^2 / W pairs per rank instead of n_val^2.
+        shard = self.world_size > 1 and bool(c.get("shard_validation", True))
+        per = (nv + self.world_size - 1) // self.world_size          # rows per rank of the sharded pair pass
         if key not in self.plans:
             V = StepPlan()
             V.enc, V.dec = self.enc.alloc(nv), self.dec.alloc(nv)
@@ -1412,8 +1413,12 @@ class StepEngine:
             V.tape.draw("normal", V.z_sample, (nv, ns))
             V.sl_disc = self.disc.tape_slots(V.tape, bc, nv, train=False)
             V.tape.finalize(dev)
-            V.rank_work = torch.empty(self._rank_work_bytes(nv), dtype=torch.uint8, device=dev)
-            V.rank_totals = torch.zeros(64, dtype=torch.float64, device=dev)
+            nbytes = self._rank_work_bytes(nv)
+            if self.aux_missing and self.world_size > 1:
+                # one buffer for the whole-set form and for this rank's share: `shard_validation` may change between calls
+                nbytes = max(nbytes, self._rank_work_bytes(max(per, 1), rows_form=True))
+            V.rank_work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            V.rank_totals = torch.zeros(80 if self.aux_missing else 64, dtype=torch.float64, device=dev)
             V.lpart = torch.zeros(RAAE_MAX_PARTS, dtype=torch.float64, device=dev)
             V.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
             V.out = torch.zeros(8, device=dev)
@@ -1437,16 +1442,17 @@ class StepEngine:
             out = self.dec.forward(V.dec, z, None, train=False)
             ops.recon_loss_fwd_bwd(val_spec, out, nv, self.L, False, V.lpart, None, fin=(1.0, V.out, 2, -1, V.ticket))
             if shard:
-                per = (nv + self.world_size - 1) // self.world_size
+                pairs, finish = ((ops.rank_rows_masked_pairs, ops.rank_rows_masked_finish) if self.aux_missing else
+                                 (ops.rank_rows_pairs, ops.rank_rows_finish))
                 row0 = min(self.rank * per, nv)
                 nrows = min(per, nv - row0)
                 if nrows > 0:
-                    ops.rank_rows_pairs(val_aux, self.n_aux, z, ns, nv, row0, nrows, self.n_aux, V.rank_work, V.rank_totals)
+                    pairs(val_aux, self.n_aux, z, ns, nv, row0, nrows, self.n_aux, V.rank_work, V.rank_totals)
                 else:                       # more ranks than validation rows: this rank adds nothing
                     V.rank_totals.zero_()
                 self._collective(V.rank_totals, "sum")
-                ops.rank_rows_finish(V.rank_totals, nv, max(nrows, 1), self.n_aux, c["kendall_activation"], 1.0,
-                                     V.rank_work, V.out[1:2], None, ns)
+                finish(V.rank_totals, nv, max(nrows, 1), self.n_aux, c["kendall_activation"], 1.0, V.rank_work,
+                       V.out[1:2], None, ns)
             elif self.aux_missing:
                 ops.rank_loss_masked_fwd_bwd(val_aux, self.n_aux, z, ns, nv, self.n_aux, c["kendall_activation"],
                                              V.rank_work, V.out[1:2], None)

@@ -224,6 +224,26 @@ def rank_rows_finish(totals, n_all, nrows, n_aux, activate, scale, work, loss, d
           "raae_rank_rows_finish")
 
 
+def rank_rows_masked_work_bytes(nrows, n_aux):
+    return int(_lib.load().raae_rank_rows_masked_work_bytes(nrows, n_aux))
+
+
+def rank_rows_masked_pairs(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, work, totals):
+    """``rank_rows_pairs`` where NaN cells of ``d_all`` are missing labels; ``totals``: 80 doubles, the fifth block of 16
+    the labelled rows per descriptor among this rank's rows."""
+    assert totals.numel() >= 80
+    check(_lib.load().raae_rank_rows_masked_pairs(_ptr(d_all), ldd, _ptr(z_all), ldz, n_all, row0, nrows, n_aux,
+                                                  _ptr(work, None), _ptr(totals, torch.float64), _stream()),
+          "raae_rank_rows_masked_pairs")
+
+
+def rank_rows_masked_finish(totals, n_all, nrows, n_aux, activate, scale, work, loss, dz, ldz):
+    assert totals.numel() >= 80
+    check(_lib.load().raae_rank_rows_masked_finish(_ptr(totals, torch.float64), n_all, nrows, n_aux, 1 if activate else 0,
+                                                   float(scale), _ptr(work, None), _ptr(loss), _ptr(dz), ldz, _stream()),
+          "raae_rank_rows_masked_finish")
+
+
 def style_metrics(z, n, k, a_coef, work, out):
     check(_lib.load().raae_style_metrics(_ptr(z), n, k, _ptr(a_coef, torch.float64), _ptr(work, torch.float64),
                                          _ptr(out, torch.float64), _stream()), "raae_style_metrics")
