@@ -1371,6 +1371,60 @@ class StepEngine:
         v = words[:8].view(torch.float32).tolist()
         return {k: v[i] for k, i in LOSS_SLOTS.items()}
 
+    def _state_buffers(self):
+        """Every module buffer of encoder, decoder and discriminator, in ``named_buffers()`` order."""
+        return [b_ for mod in (self.enc_mod, self.dec_mod, self.dis_mod) for _, b_ in mod.named_buffers()]
+
+    @_on_stream
+    def state(self):
+        """Everything a step reads that an earlier step wrote, as a plain dict of host tensors and Python scalars (the
+        engine part of a trial's resume file, ``rankaae_amd/resume.py``): the parameter arena, the module buffers, the
+        host-side BatchNorm forward counts (by position in ``enc.bn_modules + dec.bn_modules``), every optimizer's
+        moments, learning rates and step word, the device RNG state and seed, the anomaly flags.  ``loss_out``, the
+        row cursor, ``alpha_dev`` and the permutation are rewritten by ``set_epoch``: between epochs they carry
+        nothing.  One synchronisation of the engine's stream; never during a graph capture."""
+        # (this engine's own capture only: captures are thread-local -- hipStreamCaptureModeThreadLocal -- so another
+        # trial's thread capturing its step, train_sc's thread mode, does not make this synchronisation or these copies
+        # illegal, and the process-wide ops.Graph.active would be a false alarm there)
+        assert self._capture is None, "StepEngine.state() inside a graph capture"
+        torch.cuda.current_stream().synchronize()
+        opts = [self.opts[n] for n in OPT_NAMES]
+        bns = self.enc.bn_modules + self.dec.bn_modules
+        return {"arena": self.arena.P.cpu(),
+                "buffers": [b_.cpu() for b_ in self._state_buffers()],
+                "bn_counts": [int(self.bn_counts.get(id(bn), 0)) for bn in bns],
+                "opt_m": [o.m.cpu() for o in opts], "opt_v": [o.v.cpu() for o in opts],
+                "opt_lr": [float(o.lr) for o in opts], "opt_base_lr": [float(o.base_lr) for o in opts],
+                "steps_dev": self.steps_dev.cpu(), "rng_state": self.rng_state.cpu(), "seed": int(self.seed),
+                "nan_flags": self.nan_flags.cpu()}
+
+    @_on_stream
+    def load_state(self, state):
+        """Restore what ``state()`` returned, IN PLACE: the parameters are views of the arena, the exported modules
+        alias them and captured graphs hold the pointers, so every tensor is written with ``copy_`` and none is
+        rebound.  Only before the first step plan exists: the engine then captures its graphs from restored state."""
+        assert not self.plans, "StepEngine.load_state() after the first step (or validation) of this engine"
+        assert self._capture is None, "StepEngine.load_state() inside a graph capture"
+        opts = [self.opts[n] for n in OPT_NAMES]
+        bufs, bns = self._state_buffers(), self.enc.bn_modules + self.dec.bn_modules
+        pairs = ([(self.arena.P, state["arena"]), (self.steps_dev, state["steps_dev"]),
+                  (self.rng_state, state["rng_state"]), (self.nan_flags, state["nan_flags"])] +
+                 list(zip(bufs, state["buffers"])) +
+                 [(o.m, t) for o, t in zip(opts, state["opt_m"])] + [(o.v, t) for o, t in zip(opts, state["opt_v"])])
+        if (len(state["buffers"]) != len(bufs) or len(state["bn_counts"]) != len(bns) or
+                any(len(state[k]) != len(opts) for k in ("opt_m", "opt_v", "opt_lr", "opt_base_lr")) or
+                any(mine.shape != saved.shape or mine.dtype != saved.dtype for mine, saved in pairs)):
+            raise ValueError("StepEngine.load_state: the state was taken from an engine of another configuration")
+        for mine, saved in pairs:
+            mine.copy_(saved)
+        for o, lr, base_lr in zip(opts, state["opt_lr"], state["opt_base_lr"]):
+            o.lr, o.base_lr = float(lr), float(base_lr)
+            o.push()                    # `hyper` follows the restored lr / base_lr
+        self.bn_counts = {id(bn): int(n) for bn, n in zip(bns, state["bn_counts"])}
+        self.seed = int(state["seed"])
+        self._nan_host = None
+        torch.cuda.current_stream().synchronize()      # the host tensors of `state` may go once this returns
+
     @_on_stream
     def anomaly(self):
         """``None``, or ``(phase, step)``: the optimizer phase (``OPT_NAMES``) and its 1-based step count of the first

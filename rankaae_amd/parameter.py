@@ -39,6 +39,24 @@ def detect_anomaly_on(cfg):
     return value
 
 
+def checkpoint_every_of(cfg):
+    """Build-only key ``checkpoint_every`` (default 0: off): an integer N >= 0; with N > 0 ``Trainer`` writes the
+    trial's resume file (``rankaae_amd/resume.py``) after every N-th epoch, and when a stop request ends the run."""
+    value = cfg.get("checkpoint_every", 0)
+    if isinstance(value, bool) or not isinstance(value, int) or value < 0:
+        raise ValueError(f"checkpoint_every must be an integer >= 0, not {value!r}")
+    return value
+
+
+def resume_on(cfg):
+    """Build-only key ``resume`` (default ``false``): ``true`` continues a trial from the resume file in its work
+    directory, if there is a usable one."""
+    value = cfg.get("resume", False)
+    if not isinstance(value, bool):
+        raise ValueError(f"resume must be true or false, not {value!r}")
+    return value
+
+
 class Parameters:
     def __init__(self, parameter_dict):
         object.__setattr__(self, "_parameter_dict", parameter_dict)

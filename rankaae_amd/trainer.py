@@ -33,7 +33,8 @@ import torch
 from .dataloader import get_dataloaders
 from .engine import StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
-from .parameter import Parameters, check_optimizer, detect_anomaly_on
+from .parameter import Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, resume_on
+from . import resume as resume_file
 
 
 class AnomalyError(RuntimeError):
@@ -89,6 +90,15 @@ class PlateauScheduler:
                 self.opt.push()
             self.num_bad_epochs = 0
 
+    def state_dict(self):
+        """Everything ``step`` reads except the optimizer's own ``lr`` (part of the engine's state)."""
+        return {"best": float(self.best), "num_bad_epochs": int(self.num_bad_epochs), "factor": float(self.factor),
+                "patience": int(self.patience), "threshold": float(self.threshold)}
+
+    def load_state_dict(self, state):
+        self.best, self.num_bad_epochs = float(state["best"]), int(state["num_bad_epochs"])
+        self.factor, self.patience, self.threshold = float(state["factor"]), int(state["patience"]), float(state["threshold"])
+
 
 class Trainer:
     metric_weights = [1.0, -1.0, -0.01, -1.0, -1.0]
@@ -114,6 +124,13 @@ class Trainer:
         cfg = config_parameters.to_dict()
         check_optimizer(cfg)        # before anything touches the GPU
         self.detect_anomaly = detect_anomaly_on(cfg)
+        # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
+        # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
+        # the parity mode (its random tape is drawn from the global CPU generator in the reference's order)
+        self.checkpoint_every, self.resume = checkpoint_every_of(cfg), resume_on(cfg)
+        if (self.checkpoint_every or self.resume) and (self._world_size() > 1 or cfg.get("rng_mode", "philox") != "philox"):
+            raise ValueError("checkpoint_every / resume: single-process runs only")
+        self._restored, self._fingerprint = None, None
         self.world, self.rank, self.pg = self._data_parallel_setup(device)
         # one draw from the global generator per trial (also when `seed` is given, so that the generator's state
         # does not depend on the key): trials of one run then use different noise / dropout / latent streams
@@ -140,6 +157,14 @@ class Trainer:
         self.engine.set_data(ds.spec, ds.aux, aux_missing=self.aux_missing)
         self.load_optimizers()
         self.load_schedulers()
+
+    @staticmethod
+    def _world_size():
+        import torch.distributed as dist
+        world = int(os.environ.get("WORLD_SIZE", "1"))
+        if world == 1 and dist.is_available() and dist.is_initialized():
+            world = dist.get_world_size()
+        return world
 
     @staticmethod
     def _data_parallel_setup(device):
@@ -219,16 +244,85 @@ class Trainer:
 
     _gc_frozen = False
 
+    # -- the trial's resume file (config keys `checkpoint_every` / `resume`; rankaae_amd/resume.py)
+    def _resume_fingerprint(self):
+        if self._fingerprint is None:
+            eng, ds = self.engine, self.train_loader.dataset
+            self._fingerprint = resume_file.fingerprint(eng.cfg, eng.tile_mult, eng.arena.n, len(ds),
+                                                        len(self.val_loader.dataset), ds.spec)
+        return self._fingerprint
+
+    def _write_resume(self, epoch, metrics, best_combined_metric, best_chpt_file, tail_pending=False, finished=False,
+                      error=None):
+        """The state between two epochs: ``epoch`` is the last one trained and validated.  ``tail_pending``: written by
+        a stop request, which ends the run before that epoch's checkpoint rule, scheduler steps and callback -- the
+        resumed run does them first.  ``error``: the ``(phase, step, epoch)`` of the ``AnomalyError`` that ended the
+        trial; such a file holds no state (it is full of NaN) and only says that the trial is not to be trained again."""
+        state = {"version": resume_file.FORMAT_VERSION, "finished": bool(finished), "epoch": int(epoch),
+                 "error": None if error is None else [error[0], int(error[1]), int(error[2])],
+                 "tail_pending": bool(tail_pending), "metrics": None if metrics is None else [float(m) for m in metrics],
+                 "best_combined_metric": float(best_combined_metric),
+                 "best_chpt_file": None if best_chpt_file is None else os.path.basename(best_chpt_file),
+                 "checkpoint_every": int(self.checkpoint_every),
+                 "fingerprint": self._resume_fingerprint()}
+        if error is None:
+            g = getattr(self.train_loader, "generator", None)
+            state.update(engine=self.engine.state(), host_rng=g.get_state() if g is not None else torch.get_rng_state(),
+                         schedulers=[sch.state_dict() for sch in self.schedulers.values()])
+        resume_file.write_resume(self.work_dir, state)
+
+    def _restore(self, epoch=None):
+        """``resume: true``: load the newest usable generation of the trial's resume file (``epoch``: the generation of
+        that epoch -- the one a batched group agreed on; ``resume_file.FRESH``: none), check its fingerprint, and put
+        back the engine, the host generator and the schedulers.  Once per trainer, before its first step.  Returns the
+        file's dict, or False where the trial starts from epoch 0."""
+        if self._restored is not None:
+            return self._restored
+        gens = resume_file.generations(self.work_dir) if self.resume else []
+        if epoch is not None:
+            gens = [g_ for g_ in gens if int(g_[1]["epoch"]) == epoch and not g_[1].get("finished")]
+            if epoch != resume_file.FRESH and not gens:
+                raise ValueError(f"resume: {self.work_dir} has no resume file of epoch {epoch}")
+            if self.resume:
+                # a generation newer than the epoch the group agreed on goes: kept, it would stand beside the file this
+                # trial writes next, and the group's next kill could leave it without a common epoch
+                resume_file.drop_newer(self.work_dir, epoch)
+                gens = [g_ for g_ in resume_file.generations(self.work_dir) if int(g_[1]["epoch"]) == epoch] if gens else []
+        self._restored = False
+        if gens:
+            path, st = gens[0]
+            resume_file.check_fingerprint(st["fingerprint"], self._resume_fingerprint(), path)
+            if st["error"] is None:
+                self.engine.load_state(st["engine"])
+                g = getattr(self.train_loader, "generator", None)
+                if g is not None:
+                    g.set_state(st["host_rng"])
+                else:
+                    torch.set_rng_state(st["host_rng"])
+                for sch, sd in zip(self.schedulers.values(), st["schedulers"]):
+                    sch.load_state_dict(sd)
+            self.logger.info(f"Resuming from {path}: epoch {st['epoch']}" + (" (finished)" if st["finished"] else ""))
+            self._restored = st
+        return self._restored
+
     def _train_epochs(self, callback):
         from .parallel import any_rank, broadcast_from_rank0, broadcast_tensor_from_rank0, epoch_schedule
         eng = self.engine
         lead = self.rank == 0
         best_combined_metric = 10.0
         chkpt_dir = f"{self.work_dir}/checkpoints"
+        st = self._restore() if self.resume else False
+        if st and st["error"] is not None:      # the trial diverged in the earlier run: it does so again, untrained
+            raise AnomalyError(*st["error"])
+        if st and st["finished"]:
+            return list(st["metrics"])
         if lead:
             os.makedirs(chkpt_dir, exist_ok=True)
         best_chpt_file, metrics = None, None
-        if lead:
+        if lead and self.resume:
+            # rows are written every 10 epochs and the run went on after its last resume file: back to that epoch
+            resume_file.truncate_losses_csv(f"{self.work_dir}/losses.csv", st["epoch"] if st else resume_file.FRESH)
+        if lead and not st:
             self.loss_logger.info(
                 "Epoch,Train_D,Val_D,Train_G,Val_G,Train_Aux,Val_Aux,Train_Recon,"
                 "Val_Recon,Train_Smooth,Val_Smooth,Train_Mutual_Info,Val_Mutual_Info")
@@ -243,7 +337,36 @@ class Trainer:
         n_batch = len(schedule)
         bn_buffers = [b_ for mod in (self.encoder, self.decoder) for name, b_ in mod.named_buffers()
                       if name.endswith("running_mean") or name.endswith("running_var")]
-        for epoch in range(self.max_epoch):
+
+        def finish_epoch(epoch, metrics):
+            """What follows an epoch's validation: the checkpoint rule, the scheduler steps, the callback, and the
+            periodic resume file."""
+            nonlocal best_combined_metric, best_chpt_file
+            combined_metric = -(np.array(self.metric_weights) * np.array(metrics)).sum()
+            if combined_metric > best_combined_metric:
+                best_combined_metric = combined_metric
+                best_chpt_file = f"{chkpt_dir}/epoch_{epoch:06d}_loss_{combined_metric:07.6g}.pt"
+                if lead:
+                    torch.save(self._model_dict(), best_chpt_file)
+            for sch in self.schedulers.values():
+                sch.step(combined_metric)
+            if callback is not None:
+                callback(epoch, metrics)
+            if self.checkpoint_every and (epoch + 1) % self.checkpoint_every == 0:
+                self._write_resume(epoch, metrics, best_combined_metric, best_chpt_file)
+
+        first_epoch = 0
+        if st:
+            first_epoch, metrics = st["epoch"] + 1, st["metrics"]
+            best_combined_metric = st["best_combined_metric"]
+            if st["best_chpt_file"] is not None:
+                best_chpt_file = f"{chkpt_dir}/{st['best_chpt_file']}"
+            if st["tail_pending"]:          # a stop request ended the earlier run before this part of its last epoch
+                finish_epoch(st["epoch"], metrics)
+        # (the collector is held off once plans and captured graphs exist: after the second epoch of a run from
+        # scratch, after the first one of a resumed run)
+        freeze_epoch = 1 if first_epoch == 0 else first_epoch
+        for epoch in range(first_epoch, self.max_epoch):
             alpha_ = alpha(epoch / self.max_epoch, self.alpha_flat_step, self.alpha_limit)
             perm = broadcast_tensor_from_rank0(self.train_loader.epoch_permutation(), self.device, self.pg)
             eng.set_epoch(perm, alpha_)
@@ -254,7 +377,7 @@ class Trainer:
                     eng.seek(off + self.rank * rows, global_rows)
                 prev_rows = rows
                 yield ("step", rows, smooth)
-            if epoch == 1 and self.freeze_gc and not self._gc_frozen:
+            if epoch == freeze_epoch and self.freeze_gc and not self._gc_frozen:
                 # plans, captured graphs and modules are long-lived: out of the cyclic collector's way (a full
                 # collection in the middle of an epoch stalls the host for longer than the queue of launched steps lasts)
                 gc.collect()
@@ -268,6 +391,9 @@ class Trainer:
                 if self.world > 1 and any_rank(nan is not None, self.device, self.pg) and nan is None:
                     nan = (None, 0)
                 if nan is not None:
+                    if self.checkpoint_every:       # a finished file: `resume` does not train this trial again
+                        self._write_resume(epoch, None, best_combined_metric, best_chpt_file, finished=True,
+                                           error=(nan[0], nan[1], epoch))
                     raise AnomalyError(nan[0], nan[1], epoch)
             if not smooth:
                 tl["smooth"] = 0.0
@@ -296,21 +422,17 @@ class Trainer:
                 # others waiting in the next step's all-reduce)
                 raise Exception(self._stop_reason or "Training Overtime!")
             if self.world == 1 and self._stop_reason is not None:      # thread mode of train_sc: a timer asked for it
+                if self.checkpoint_every:       # what the GPU computed so far stays: the resumed run finishes this epoch
+                    self._write_resume(epoch, metrics, best_combined_metric, best_chpt_file, tail_pending=True)
                 raise Exception(self._stop_reason)
-            combined_metric = -(np.array(self.metric_weights) * np.array(metrics)).sum()
-            if combined_metric > best_combined_metric:
-                best_combined_metric = combined_metric
-                best_chpt_file = f"{chkpt_dir}/epoch_{epoch:06d}_loss_{combined_metric:07.6g}.pt"
-                if lead:
-                    torch.save(self._model_dict(), best_chpt_file)
-            for sch in self.schedulers.values():
-                sch.step(combined_metric)
-            if callback is not None:
-                callback(epoch, metrics)
+            finish_epoch(epoch, metrics)
         if lead:
             torch.save(self._model_dict(), f"{self.work_dir}/final.pt")
             if best_chpt_file is not None:
                 shutil.copy2(best_chpt_file, f"{self.work_dir}/best.pt")
+            if self.checkpoint_every and metrics is not None:
+                # `resume` (train_sc) skips a trial whose file says so
+                self._write_resume(self.max_epoch - 1, metrics, best_combined_metric, best_chpt_file, finished=True)
         return metrics
 
     @classmethod
@@ -354,6 +476,15 @@ def train_trials_batched(trainers, callbacks=None):
     (and written their files) ``TrialsDiverged`` carries every trial's metrics or error."""
     from .trial_batch import TrialBatch
     callbacks = callbacks or [None] * len(trainers)
+    if any(t.resume for t in trainers):
+        # the trials advance together, so they resume from ONE epoch: the greatest that every member's two generations
+        # of resume files offer (the engines are restored here, before the batch is built)
+        if any(resume_file.finished_state(t.work_dir) is not None for t in trainers):
+            raise ValueError("resume: a trial of the batch has finished (or diverged) already; leave it out of the group")
+        common = resume_file.choose_group_epoch([resume_file.offered_epochs(t.work_dir) if t.resume else
+                                                 [resume_file.FRESH] for t in trainers])
+        for t in trainers:
+            t._restore(common)
     batch = TrialBatch([t.engine for t in trainers])
     gens = [t._train_epochs(cb) for t, cb in zip(trainers, callbacks)]
     T = len(trainers)
@@ -367,6 +498,30 @@ def train_trials_batched(trainers, callbacks=None):
         except AnomalyError as exc:
             errors[i] = exc
         return None
+
+    def advance_all(answers):
+        """Every live trial one request further.  A stop request that ends one trial ends the batch; with resume files
+        on, the others are asked to stop too and write theirs at this epoch before the exception goes on."""
+        out, stopped = [None] * T, None
+        for i in range(T):
+            if reqs[i] is None:
+                continue
+            try:
+                out[i] = advance(i, answers[i])
+            except Exception as exc:      # noqa: BLE001 -- re-raised below, or here
+                # only the stop exception itself (`raise Exception(reason)` of _train_epochs): a failed file write, say,
+                # propagates as it is
+                if type(exc) is not Exception or trainers[i]._stop_reason is None or str(exc) != str(trainers[i]._stop_reason):
+                    raise
+                if stopped is None:
+                    if not trainers[i].checkpoint_every:
+                        raise
+                    stopped = exc
+                    for t in trainers[i + 1:]:
+                        t.request_stop(trainers[i]._stop_reason)
+        if stopped is not None:
+            raise stopped
+        return out
 
     try:
         reqs = [advance(i, None) for i in range(T)]
@@ -393,7 +548,7 @@ def train_trials_batched(trainers, callbacks=None):
                 # (raae_metrics.hip), counts comparisons that are false for NaN and stays in [0, n)
                 val = [reqs[i][1:] if reqs[i] is not None else trainers[i]._val_split for i in range(T)]
                 answers = batch.validate([v[0] for v in val], [v[1] for v in val])
-            reqs = [advance(i, answers[i]) if reqs[i] is not None else None for i in range(T)]
+            reqs = advance_all(answers)
         if any(e is not None for e in errors):
             raise TrialsDiverged(results, errors)
         return results
