@@ -587,8 +587,8 @@ __device__ __forceinline__ void dense_bwd_body(const DenseBwdArgs& a, float* sme
                     const size_t o = (size_t)row * a.N + n;
                     const float gv = a.g[o];
                     if (a.g_kind == RAAE_G_DIRECT) dz = gv;
-                    else if (a.g_kind == RAAE_G_SOFTPLUS) dz = gv * (1.f - expf(-2.f * a.zout[o]));
-                    else if (a.g_kind == RAAE_G_RELU) dz = a.zout[o] > 0.f ? gv : 0.f;
+                    else if (a.g_kind == RAAE_G_SOFTPLUS) dz = gv * (1.f - expf(-2.f * (zb ? bf16_at(a.zout, o) : a.zout[o])));
+                    else if (a.g_kind == RAAE_G_RELU) dz = (zb ? bf16_at(a.zout, o) : a.zout[o]) > 0.f ? gv : 0.f;
                     else {
                         const float zv = zb ? bf16_at(a.zout, o) : a.zout[o];
                         float da = gv;
