@@ -74,6 +74,11 @@ PHASE_OF = {"adversarial": "adversarial", "correlation": "kendall", "reconstruct
 INLINE_CASES = {
     "compact_nstyle5": dict(n_rows=420, n_points=256, data_seed=2, model_seed=31,
                             over=dict(ae_form="compact", nstyle=5, n_aux=3, batch_size=48)),
+    # nstyle = 13 (the style count the project trains on FC, ref_fc_512_aux12): the first decoder block is 13 -> 8
+    # channels, more than the tiled kernels take, so it runs per layer and its length-axis Linear (forward with
+    # statistics, weight gradient) and the data gradient of its convolutions run the GENERIC per-layer kernels
+    "compact_nstyle13": dict(n_rows=420, n_points=256, data_seed=3, model_seed=33,
+                             over=dict(ae_form="compact", nstyle=13, n_aux=12, batch_size=48)),
     # BASELINE configs[2]'s batch (4096 rows): the HBM-bound regime -- strip convolution kernel, 512-workgroup
     # grids, hundreds of gradient slabs per parameter, Adam's lane-split slab sum.
     "compact_b4096": dict(n_rows=6000, n_points=256, data_seed=4, model_seed=41,
@@ -278,7 +283,7 @@ def oracle_float64_gradients(spec, aux, cfg, pre_state, post_states, tape, rows,
 @pytest.mark.parametrize("case,steps", [("fc_small", (1, 2, 5, 8)), ("fc_adam_nodrop", (1, 3)), ("fc_512_aux12", (2,)),
                                         ("compact_small", (1, 2, 5, 8)), ("compact_nstyle5", (1, 3)),
                                         ("compact_b4096", (1,)), ("fc_b4096", (1,)), ("fc_example", (1, 5)),
-                                        ("compact_b1024", (1,))])
+                                        ("compact_b1024", (1,)), ("compact_nstyle13", (1, 3))])
 def test_p2_teacher_forced_steps(case, steps):
     _p2(case, steps, use_graph=False)
 
@@ -535,7 +540,7 @@ def _p2(case, steps, use_graph):
                     assert torch.allclose(val.cpu(), sd[key], rtol=1e-4, atol=1e-6), (case, k, key)
 
 
-@pytest.mark.parametrize("case", ["fc_small", "compact_small", "compact_nstyle5"])
+@pytest.mark.parametrize("case", ["fc_small", "compact_small", "compact_nstyle5", "compact_nstyle13"])
 def test_graph_replay_is_bitwise_eager(case):
     """The captured hipGraph replays the very same program: after 6 steps (3 of them replays, last
     one a ragged batch through a second plan) weights and losses are BITWISE those of eager launches,
@@ -641,7 +646,7 @@ def test_one_row_batch_raises_like_the_reference():
 
 
 @pytest.mark.parametrize("case,extra", [("compact_small", {}), ("fc_small", {}), ("compact_nstyle5", {}),
-                                        ("compact_small", {"fused_blocks": False})])
+                                        ("compact_small", {"fused_blocks": False}), ("compact_nstyle13", {})])
 def test_paired_forwards_change_nothing(case, extra):
     """The two forward chains whose results the reference discards run in lockstep with a needed forward chain
     (one launch per pair of block kernels; the decoder one is deferred from before phase A into phase B).  Same
@@ -884,7 +889,8 @@ def test_bf16_storage_mode_fc_512_aux12():
         build_engine(dict(load_case("compact_small")[1], precision="bf16"), 1, *load_case("compact_small")[2:])
 
 
-@pytest.mark.parametrize("case", ["fc_small", "compact_small", "compact_nstyle5", "fc_example"])
+@pytest.mark.parametrize("case", ["fc_small", "compact_small", "compact_nstyle5", "compact_nstyle13",
+                                  "fc_example"])
 def test_reads_between_steps_change_nothing(case):
     """A free-running graph-replay run -- three epochs of full batches and a ragged one (another plan), the last epoch
     without the smoothness phase, a read of the losses in the middle of an epoch and a validation between epochs --
