@@ -343,6 +343,28 @@ int raae_optim_step(float* p, float* m, float* v, const float* g_slabs, long sla
 int raae_optim_step_chk(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
                         const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
                         int max_nslab, int* nan_step, void* stream);
+/* ---- gradient-norm clipping (ABI 26; config key `grad_clip_norm`) ----
+ * raae_grad_norm: the L2 norm of an optimizer's gradient as the update kernels see it -- element i = the fixed-order
+ * fp32 sum of seg_nslab[i/64] slabs, summed in the order the update with the same max_nslab sums them (0 slabs: not
+ * counted) -- squares accumulated in double in a fixed order, so the result does not depend on how the workgroups are
+ * scheduled (no float atomics) and two launches on the same data give the same bits.
+ *   max_norm: finite, > 0.
+ *   partial (device, RAAE_GRAD_NORM_PARTS doubles) and ticket (device unsigned, zero before the first call; the launch
+ *   leaves it zero): scratch of ONE launch at a time.
+ *   out (device, 2 floats) = {norm, scale}, scale = min(1, max_norm / (norm + 1e-6)): what
+ *   torch.nn.utils.clip_grad_norm_ multiplies the gradients by.  A NaN gradient gives a NaN norm and a NaN scale.
+ *   clipped (device int): += 1 when scale < 1. */
+#define RAAE_GRAD_NORM_PARTS 256
+int raae_grad_norm(const float* g_slabs, long slab_stride, const unsigned short* seg_nslab, long n, int max_nslab,
+                   double max_norm, double* partial, unsigned* ticket, float* out, int* clipped, void* stream);
+/* raae_optim_step / raae_optim_step_chk with a gradient scale (ABI 26): every element's slab-summed gradient is
+ * multiplied by *scale (device float, e.g. out + 1 of raae_grad_norm) before weight decay and the moments; a decoupled
+ * decay does not see it.  The NaN check (nan_step != NULL) looks at the gradient before the scale, and a NaN gradient
+ * stays NaN.  nan_step == NULL: unchecked.  scale == NULL: exactly raae_optim_step (nan_step == NULL) or
+ * raae_optim_step_chk, the same launches; with *scale == 1.0f the update is bit for bit theirs. */
+int raae_optim_step_clip(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                         const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
+                         int max_nslab, int* nan_step, const float* scale, void* stream);
 /* ====================== 1-D convolutional networks (ae_form: compact) ======================
  * Activations are [B][C][L] fp32, stored RAW (pre-activation); what a consumer sees is a *view*:
  *     value = mask * BatchNorm( PReLU(raw, slope_c) )          (each stage optional)
@@ -594,7 +616,7 @@ int raae_step_begin(const raae_step_begin_t* p, void* stream);
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk)) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, and since ABI 26 raae_slab_reduce) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -639,7 +661,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 25
+#define RAAE_ABI_VERSION 26
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

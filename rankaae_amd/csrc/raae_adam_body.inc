@@ -7,7 +7,19 @@
 // Gradient of element i = fixed-order sum of seg_nslab[i/64] slabs; 0 slabs => parameter is
 // skipped (the reference skips params whose .grad is None, trainer.py:318-321).
 struct AdamArgs { float* p; float* m; float* v; const float* g_slabs; long slab_stride; const unsigned short* seg_nslab;
-                  long n; const double* hyper; const int* step; int decoupled; };
+                  long n; const double* hyper; const int* step; int decoupled;
+                  const float* gscale; };   // NULL, or the clip scale of raae_grad_norm (read by the SC = true instances only)
+
+// Gradient clipping (SC = true; raae_optim_step_clip): the slab-summed gradient times *gscale, the scale raae_grad_norm
+// left, before weight decay and the moments; the NaN check looks at the gradient before the scale.  The product is
+// handed on through an empty asm statement: the update that follows then compiles as it does on the slab sum itself
+// (the product is never contracted into an add, never packed with another multiply), so that a scale of exactly 1.0f
+// gives the bits of the instance without a scale.
+__device__ __forceinline__ float scale_grad(float g, float gs) {
+    float r = g * gs;
+    asm volatile("" : "+v"(r));
+    return r;
+}
 
 // NaN check of the checked instances (CHK = true; raae_optim_step_chk): every lane keeps whether a gradient it summed
 // was NaN, the wave votes once after its loop, and one lane of a wave that saw one writes the optimizer's step count
@@ -21,10 +33,11 @@ __device__ __forceinline__ void nan_vote(bool seen, int* nan_step, const int* st
 struct AdamChkArgs { AdamArgs a; int* nan_step; };
 
 // Same update with the slabs of an element spread over 8 lanes: for ranges whose tensors have many slabs.
-template <bool CHK>
+template <bool CHK, bool SC = false>
 __device__ __forceinline__ void adam_wide_body(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
                                                const unsigned short* seg_nslab, long n, const double* hyper,
-                                               const int* step, int decoupled, int* nan_step, const int bx, const int gx) {
+                                               const int* step, int decoupled, int* nan_step, const int bx, const int gx,
+                                               const float* gscale = nullptr) {
     __shared__ float s_sc[8];
     if (threadIdx.x == 0) {
         const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
@@ -48,6 +61,8 @@ __device__ __forceinline__ void adam_wide_body(float* p, float* m, float* v, con
     const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;
     const long wave0 = ((long)bx * 4 + (threadIdx.x >> 6)) * 8;
     bool seen = false;
+    float gs = 1.f;
+    if (SC) gs = gscale[0];
     for (long base = wave0; base < n; base += (long)gx * 32) {
         // No contraction into fma: as compiled into adam_wide_kernel none of the multiply-adds below is contracted (the
         // packed multiplies and adds come first), inlined into another kernel some are -- pinned, so that the update
@@ -72,6 +87,7 @@ __device__ __forceinline__ void adam_wide_body(float* p, float* m, float* v, con
         g += __shfl_xor(g, 32, 64);
         if (ch != 0) continue;
         if (CHK) seen |= __builtin_isnan(g);
+        if (SC) g = scale_grad(g, gs);
         float pv = p[i];
         if (decoupled) pv = pv * decay; else if (wdf != 0.f) g = g + wdf * pv;
         float mv = m[i], vv = v[i];

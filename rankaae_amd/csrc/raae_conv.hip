@@ -1148,6 +1148,7 @@ static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
         s.ad.a.p = p->p; s.ad.a.m = p->m; s.ad.a.v = p->v; s.ad.a.g_slabs = p->g_slabs; s.ad.a.slab_stride = p->slab_stride;
         s.ad.a.seg_nslab = p->seg_nslab; s.ad.a.n = p->n; s.ad.a.hyper = p->hyper; s.ad.a.step = p->step;
         s.ad.a.decoupled = p->rule == RAAE_OPT_ADAMW;
+        s.ad.a.gscale = nullptr;               // (a clipped update never rides: it follows its norm launch)
         s.ad.nan_step = p->nan_step;
         s.chk = p->nan_step != nullptr;
         s.wide = p->max_nslab > 16;

@@ -9,10 +9,10 @@ namespace {
 #include "raae_adam_body.inc"
 
 
-template <bool CHK>
+template <bool CHK, bool SC = false>
 __device__ __forceinline__ void adam_body(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
                                           const unsigned short* seg_nslab, long n, const double* hyper,
-                                          const int* step, int decoupled, int* nan_step) {
+                                          const int* step, int decoupled, int* nan_step, const float* gscale = nullptr) {
     __shared__ float s_sc[8];
     if (threadIdx.x == 0) {
         const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
@@ -31,6 +31,8 @@ __device__ __forceinline__ void adam_body(float* p, float* m, float* v, const fl
     const float decay = s_sc[0], w1 = s_sc[1], b2f = s_sc[2], omb2 = s_sc[3], nstep = s_sc[4], bc2s = s_sc[5],
                 epsf = s_sc[6], wdf = s_sc[7];
     bool seen = false;
+    float gs = 1.f;
+    if (SC) gs = gscale[0];                 // the clip scale raae_grad_norm left (scale_grad: raae_adam_body.inc)
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int ns = seg_nslab[i >> 6];
         if (ns == 0) continue;
@@ -46,6 +48,7 @@ __device__ __forceinline__ void adam_body(float* p, float* m, float* v, const fl
         }
         for (; s < ns; ++s) g += g_slabs[(size_t)s * slab_stride + i];
         if (CHK) seen |= __builtin_isnan(g);
+        if (SC) g = scale_grad(g, gs);
         float pv = p[i];
         if (decoupled) pv = pv * decay; else if (wdf != 0.f) g = g + wdf * pv;
         float mv = m[i], vv = v[i];
@@ -97,13 +100,29 @@ __global__ __launch_bounds__(256) void adam_wide_chk_kernel_m(const AdamChkArgs*
                          c.nan_step, blockIdx.x, gridDim.x);
 }
 
+// clipped instances (raae_optim_step_clip with a scale): the bodies above with SC = true, checked or not, narrow or wide
+template <bool CHK, bool WIDE>
+__device__ __forceinline__ void adam_clip_run(const AdamChkArgs& c) {
+    const AdamArgs& a = c.a;
+    if (WIDE) adam_wide_body<CHK, true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
+                                        c.nan_step, blockIdx.x, gridDim.x, a.gscale);
+    else adam_body<CHK, true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
+                              c.nan_step, a.gscale);
+}
+template <bool CHK, bool WIDE> __global__ __launch_bounds__(256) void adam_clip_kernel(AdamChkArgs c) { adam_clip_run<CHK, WIDE>(c); }
+template <bool CHK, bool WIDE> __global__ __launch_bounds__(256) void adam_clip_kernel_m(const AdamChkArgs* t) {
+    const AdamChkArgs c = t[blockIdx.z];
+    adam_clip_run<CHK, WIDE>(c);
+}
+
 // ---- RAdam and AdaBound (torch_optimizer 0.1.0, the optimizer_name values the reference takes from that package) ----
 // One kernel instance per rule: OptRule<R>::scalars forms the per-step scalars in double (Python floats) from the
 // device hyper block and step count, in the operation order of the Python source (no contraction into fma there);
 // OptRule<R>::update is the per-element fp32 update in the order of the torch ops.  Gradient reading as in Adam.
 constexpr int OPT_NSC = 10;
 struct OptimArgs { float* p; float* m; float* v; const float* g_slabs; long slab_stride; const unsigned short* seg_nslab;
-                   long n; const double* hyper; const int* step; };
+                   long n; const double* hyper; const int* step;
+                   const float* gscale; };  // NULL, or the clip scale (AdamArgs::gscale)
 template <int RULE> struct OptRule;
 
 // torch_optimizer.RAdam.step.  The class caches (t, N, step size) in a 10-entry buffer keyed on t % 10, filled by the
@@ -188,11 +207,13 @@ __device__ __forceinline__ void optim_scalars(const OptimArgs& a, float (&sc)[OP
     for (int k = 0; k < OPT_NSC; ++k) sc[k] = s_sc[k];
 }
 
-template <int RULE, bool CHK>
+template <int RULE, bool CHK, bool SC = false>
 __device__ __forceinline__ void optim_body(const OptimArgs& a, int* nan_step) {
     float sc[OPT_NSC];
     optim_scalars<RULE>(a, sc);
     bool seen = false;
+    float gs = 1.f;
+    if (SC) gs = a.gscale[0];
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
         const int ns = a.seg_nslab[i >> 6];
         if (ns == 0) continue;
@@ -207,6 +228,7 @@ __device__ __forceinline__ void optim_body(const OptimArgs& a, int* nan_step) {
         }
         for (; s < ns; ++s) g += a.g_slabs[(size_t)s * a.slab_stride + i];
         if (CHK) seen |= __builtin_isnan(g);
+        if (SC) g = scale_grad(g, gs);
         float pv = a.p[i], mv = a.m[i], vv = a.v[i];
         OptRule<RULE>::update(sc, pv, mv, vv, g);
         a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
@@ -214,10 +236,12 @@ __device__ __forceinline__ void optim_body(const OptimArgs& a, int* nan_step) {
     if (CHK) nan_vote(seen, nan_step, a.step);
 }
 
-template <int RULE, bool CHK>
+template <int RULE, bool CHK, bool SC = false>
 __device__ __forceinline__ void optim_wide_body(const OptimArgs& a, int* nan_step) {
     float sc[OPT_NSC];
     optim_scalars<RULE>(a, sc);
+    float gs = 1.f;
+    if (SC) gs = a.gscale[0];
     const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;   // adam_wide_body's lane split and shuffle tree
     const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
     bool seen = false;
@@ -241,6 +265,7 @@ __device__ __forceinline__ void optim_wide_body(const OptimArgs& a, int* nan_ste
         g += __shfl_xor(g, 32, 64);
         if (ch != 0) continue;
         if (CHK) seen |= __builtin_isnan(g);
+        if (SC) g = scale_grad(g, gs);
         float pv = a.p[i], mv = a.m[i], vv = a.v[i];
         OptRule<RULE>::update(sc, pv, mv, vv, g);
         a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
@@ -275,6 +300,15 @@ template <int RULE> __global__ __launch_bounds__(256) void optim_wide_chk_kernel
     optim_wide_body<RULE, true>(c.a, c.nan_step);
 }
 
+// clipped instances (raae_optim_step_clip with a scale)
+template <int RULE, bool CHK, bool WIDE> __global__ __launch_bounds__(256) void optim_clip_kernel(OptimChkArgs c) {
+    if (WIDE) optim_wide_body<RULE, CHK, true>(c.a, c.nan_step); else optim_body<RULE, CHK, true>(c.a, c.nan_step);
+}
+template <int RULE, bool CHK, bool WIDE> __global__ __launch_bounds__(256) void optim_clip_kernel_m(const OptimChkArgs* t) {
+    const OptimChkArgs c = t[blockIdx.z];
+    if (WIDE) optim_wide_body<RULE, CHK, true>(c.a, c.nan_step); else optim_body<RULE, CHK, true>(c.a, c.nan_step);
+}
+
 // the grid of every update kernel: above 16 slabs 32 elements per workgroup (8 lanes per element), else one per thread
 inline dim3 optim_grid(long n, int max_nslab) {
     long g = max_nslab > 16 ? (n + 31) / 32 : (n + 255) / 256;
@@ -302,6 +336,108 @@ void launch_optim_chk(const OptimChkArgs& c, int max_nslab, hipStream_t stream) 
                      stream, c);
     else
         raae::launch(optim_chk_kernel<RULE>, optim_chk_kernel_m<RULE>, optim_grid(c.a.n, max_nslab), dim3(256), 0, stream, c);
+}
+
+template <int RULE>
+void launch_optim_clip(const OptimChkArgs& c, int max_nslab, hipStream_t stream) {
+    const dim3 grid = optim_grid(c.a.n, max_nslab), block(256);
+    if (max_nslab > 16) {
+        if (c.nan_step) raae::launch(optim_clip_kernel<RULE, true, true>, optim_clip_kernel_m<RULE, true, true>, grid, block, 0, stream, c);
+        else raae::launch(optim_clip_kernel<RULE, false, true>, optim_clip_kernel_m<RULE, false, true>, grid, block, 0, stream, c);
+    } else {
+        if (c.nan_step) raae::launch(optim_clip_kernel<RULE, true, false>, optim_clip_kernel_m<RULE, true, false>, grid, block, 0, stream, c);
+        else raae::launch(optim_clip_kernel<RULE, false, false>, optim_clip_kernel_m<RULE, false, false>, grid, block, 0, stream, c);
+    }
+}
+
+// ---- gradient-norm clipping (config key `grad_clip_norm`): the L2 norm of an optimizer's slab-summed gradient ----
+// Every lane sums the slabs of its elements in fp32 in the update kernels' order (one thread per element, or 8 lanes
+// per element and their shuffle tree above 16 slabs) and accumulates the squares in double; the lanes meet in the
+// xor-shuffle tree of a wave, the waves in LDS in wave order, and thread 0 stores the workgroup's partial.  The last
+// workgroup to arrive (ticket, as the loss kernels' loss_fin_last_block) adds the partials -- thread t takes partials t,
+// t + 256, ..., then the same tree -- and writes out = {norm, scale}, scale = min(1, max_norm / (norm + 1e-6)) (what
+// torch.nn.utils.clip_grad_norm_ multiplies by; NaN for a NaN norm, as there), counts the step in *clipped when
+// scale < 1 and resets the ticket for the next launch (graph replay).  No float atomics: the arrival order decides only
+// WHO adds the partials, never the order in which they are added.
+constexpr int GRAD_NORM_PARTS = RAAE_GRAD_NORM_PARTS;
+struct GradNormArgs { const float* g_slabs; long slab_stride; const unsigned short* seg_nslab; long n; double max_norm;
+                      double* partial; unsigned* ticket; float* out; int* clipped; };
+template <bool WIDE>
+__device__ __forceinline__ void grad_norm_body(const GradNormArgs& a) {
+    __shared__ double s_red[16];
+    __shared__ unsigned s_last;
+    double acc = 0.0;
+    if (!WIDE) {
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
+            const int ns = a.seg_nslab[i >> 6];
+            if (ns == 0) continue;
+            float g = 0.f;                                  // adam_body's fixed-order slab sum
+            int s = 0;
+            for (; s + 8 <= ns; s += 8) {
+                float t[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) t[u] = a.g_slabs[(size_t)(s + u) * a.slab_stride + i];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) g += t[u];
+            }
+            for (; s < ns; ++s) g += a.g_slabs[(size_t)s * a.slab_stride + i];
+            acc += (double)g * (double)g;
+        }
+    } else {
+        const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;   // adam_wide_body's lane split and shuffle tree
+        const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+        for (long base = wave0; base < a.n; base += (long)gridDim.x * 32) {
+            const long i = base + el;                       // n is a multiple of 64: i < n whenever base < n
+            const int ns = a.seg_nslab[i >> 6];
+            if (ns == 0) continue;                          // uniform over the wave (8 elements share a segment)
+            float g = 0.f;
+            for (int s = ch; s < ns; s += 64) {
+                float t[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const int r = s + 8 * u;
+                    t[u] = a.g_slabs[(size_t)(r < ns ? r : ch) * a.slab_stride + i];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) g += (s + 8 * u < ns) ? t[u] : 0.f;
+            }
+            g += __shfl_xor(g, 8, 64);
+            g += __shfl_xor(g, 16, 64);
+            g += __shfl_xor(g, 32, 64);
+            if (ch == 0) acc += (double)g * (double)g;
+        }
+    }
+    const double part = raae::block_sum(acc, s_red);
+    if (threadIdx.x == 0) {
+        a.partial[blockIdx.x] = part;
+        __threadfence();
+        s_last = atomicAdd(a.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!s_last) return;                     // uniform per workgroup
+    __threadfence();
+    double t = 0.0;
+    for (unsigned i = threadIdx.x; i < gridDim.x; i += 256) t += ((volatile double*)a.partial)[i];
+    t = raae::block_sum(t, s_red);
+    if (threadIdx.x == 0) {
+        const double norm = sqrt(t);
+        const double r = a.max_norm / (norm + 1e-6);
+        const float scale = (float)(r < 1.0 ? r : (r != r ? r : 1.0));
+        a.out[0] = (float)norm;
+        a.out[1] = scale;
+        if (scale < 1.f) a.clipped[0] += 1;
+        *a.ticket = 0u;
+    }
+}
+__global__ __launch_bounds__(256) void grad_norm_kernel(GradNormArgs a) { grad_norm_body<false>(a); }
+__global__ __launch_bounds__(256) void grad_norm_kernel_m(const GradNormArgs* t) {
+    const GradNormArgs a = t[blockIdx.z];
+    grad_norm_body<false>(a);
+}
+__global__ __launch_bounds__(256) void grad_norm_wide_kernel(GradNormArgs a) { grad_norm_body<true>(a); }
+__global__ __launch_bounds__(256) void grad_norm_wide_kernel_m(const GradNormArgs* t) {
+    const GradNormArgs a = t[blockIdx.z];
+    grad_norm_body<true>(a);
 }
 
 __global__ void tick_kernel(int* steps, int n, unsigned mask, unsigned long long* rng_counter, int* cursor,
@@ -539,6 +675,45 @@ extern "C" int raae_optim_step_chk(float* p, float* m, float* v, const float* g_
     RAAE_LAUNCH_RET();
 }
 
+extern "C" int raae_optim_step_clip(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                                    const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
+                                    int max_nslab, int* nan_step, const float* scale, void* stream) {
+    if (scale == nullptr)               // no scale: the entries without one, launch for launch
+        return nan_step ? raae_optim_step_chk(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab, nan_step, stream)
+                        : raae_optim_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab, stream);
+    RAAE_CHECK_ARG(rule >= RAAE_OPT_ADAM && rule <= RAAE_OPT_ADABOUND);
+    RAAE_CHECK_ARG(p && m && v && g_slabs && seg_nslab && hyper && step && n > 0 && (n % 64) == 0 && max_nslab >= 0);
+    const hipStream_t st = (hipStream_t)stream;
+    if (rule == RAAE_OPT_ADAM || rule == RAAE_OPT_ADAMW) {
+        const AdamChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, rule == RAAE_OPT_ADAMW, scale}, nan_step};
+        const dim3 grid = optim_grid(n, max_nslab), block(256);
+        if (max_nslab > 16) {
+            if (nan_step) raae::launch(adam_clip_kernel<true, true>, adam_clip_kernel_m<true, true>, grid, block, 0, st, c);
+            else raae::launch(adam_clip_kernel<false, true>, adam_clip_kernel_m<false, true>, grid, block, 0, st, c);
+        } else {
+            if (nan_step) raae::launch(adam_clip_kernel<true, false>, adam_clip_kernel_m<true, false>, grid, block, 0, st, c);
+            else raae::launch(adam_clip_kernel<false, false>, adam_clip_kernel_m<false, false>, grid, block, 0, st, c);
+        }
+    } else {
+        const OptimChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, scale}, nan_step};
+        if (rule == RAAE_OPT_RADAM) launch_optim_clip<RAAE_OPT_RADAM>(c, max_nslab, st);
+        else launch_optim_clip<RAAE_OPT_ADABOUND>(c, max_nslab, st);
+    }
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_grad_norm(const float* g_slabs, long slab_stride, const unsigned short* seg_nslab, long n, int max_nslab,
+                              double max_norm, double* partial, unsigned* ticket, float* out, int* clipped, void* stream) {
+    RAAE_CHECK_ARG(g_slabs && seg_nslab && partial && ticket && out && clipped && n > 0 && (n % 64) == 0 && max_nslab >= 0);
+    RAAE_CHECK_ARG(max_norm > 0.0 && max_norm <= 1.7976931348623157e308);      // finite, > 0 (false for NaN)
+    const GradNormArgs a = {g_slabs, slab_stride, seg_nslab, n, max_norm, partial, ticket, out, clipped};
+    long g = max_nslab > 16 ? (n + 31) / 32 : (n + 255) / 256;      // the update kernels' split of the elements ...
+    if (g > GRAD_NORM_PARTS) g = GRAD_NORM_PARTS;                   // ... over at most as many workgroups as `partial` holds
+    if (max_nslab > 16) raae::launch(grad_norm_wide_kernel, grad_norm_wide_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
+    else raae::launch(grad_norm_kernel, grad_norm_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
+    RAAE_LAUNCH_RET();
+}
+
 extern "C" int raae_step_tick(int* steps, int n, unsigned mask, unsigned long long* rng_counter, int* cursor,
                               int cursor_inc, void* stream) {
     RAAE_CHECK_ARG(steps && n >= 0 && n <= 32);
@@ -635,8 +810,10 @@ extern "C" const char* raae_source_digest(void) { return RAAE_SOURCE_DIGEST; }
 
 // ---------------------------------------------------------------- data-parallel helper
 namespace {
-__global__ __launch_bounds__(256) void slab_reduce_kernel(const float* g_slabs, long slab_stride,
-                                                          const unsigned short* seg_nslab, long n, float* out) {
+// (argument block + `_m` twins: with `grad_clip_norm` the flat gradient is part of a batched trial's step too)
+struct SlabReduceArgs { const float* g_slabs; long slab_stride; const unsigned short* seg_nslab; long n; float* out; };
+__device__ __forceinline__ void slab_reduce_body(const float* g_slabs, long slab_stride,
+                                                 const unsigned short* seg_nslab, long n, float* out) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
         const int ns = seg_nslab[i >> 6];
         float g = 0.f;
@@ -654,8 +831,8 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* g_slabs, 
 }
 // the summation tree of adam_wide_kernel (8 lanes per element), so that the data-parallel path adds the
 // slabs of a rank in exactly the order the single-GPU update does
-__global__ __launch_bounds__(256) void slab_reduce_wide_kernel(const float* g_slabs, long slab_stride,
-                                                               const unsigned short* seg_nslab, long n, float* out) {
+__device__ __forceinline__ void slab_reduce_wide_body(const float* g_slabs, long slab_stride,
+                                                      const unsigned short* seg_nslab, long n, float* out) {
     const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;
     const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
     for (long base = wave0; base < n; base += (long)gridDim.x * 32) {
@@ -678,21 +855,34 @@ __global__ __launch_bounds__(256) void slab_reduce_wide_kernel(const float* g_sl
         if (ch == 0) out[i] = g;
     }
 }
+__global__ __launch_bounds__(256) void slab_reduce_kernel(SlabReduceArgs a) {
+    slab_reduce_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
+}
+__global__ __launch_bounds__(256) void slab_reduce_kernel_m(const SlabReduceArgs* t) {
+    const SlabReduceArgs a = t[blockIdx.z];
+    slab_reduce_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
+}
+__global__ __launch_bounds__(256) void slab_reduce_wide_kernel(SlabReduceArgs a) {
+    slab_reduce_wide_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
+}
+__global__ __launch_bounds__(256) void slab_reduce_wide_kernel_m(const SlabReduceArgs* t) {
+    const SlabReduceArgs a = t[blockIdx.z];
+    slab_reduce_wide_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
+}
 }  // namespace
 
 extern "C" int raae_slab_reduce(const float* g_slabs, long slab_stride, const unsigned short* seg_nslab, long n,
                                 float* out, int max_nslab, void* stream) {
     RAAE_CHECK_ARG(g_slabs && seg_nslab && out && n > 0 && (n % 64) == 0 && max_nslab >= 0);
+    const SlabReduceArgs a = {g_slabs, slab_stride, seg_nslab, n, out};
     if (max_nslab > 16) {
         long g = (n + 31) / 32;
         if (g > 4096) g = 4096;
-        RAAE_PLAIN_LAUNCH(slab_reduce_wide_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, g_slabs, slab_stride,
-                           seg_nslab, n, out);
+        raae::launch(slab_reduce_wide_kernel, slab_reduce_wide_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
     } else {
         long g = (n + 255) / 256;
         if (g > 4096) g = 4096;
-        RAAE_PLAIN_LAUNCH(slab_reduce_kernel, dim3((int)g), dim3(256), 0, (hipStream_t)stream, g_slabs, slab_stride,
-                           seg_nslab, n, out);
+        raae::launch(slab_reduce_kernel, slab_reduce_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
     }
     RAAE_LAUNCH_RET();
 }

@@ -26,7 +26,7 @@ from torch import nn
 from . import _lib, ops, schedule
 from .metrics import StyleMetrics
 from .schedule import Pass
-from .parameter import check_optimizer, detect_anomaly_on
+from .parameter import check_optimizer, detect_anomaly_on, grad_clip_norm_of
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -493,9 +493,22 @@ class StepEngine:
         self.arena = Arena([("disc", discriminator), ("enc", encoder), ("dec", decoder)], device)
         self.max_slab = 512
         self.G = torch.zeros(self.max_slab, self.arena.n, device=device)
-        if self.world_size > 1:
+        # build-only key `grad_clip_norm` (default absent: off): every optimizer clips the L2 norm of its own gradient
+        # before its update (`_adam`).  The norm needs the gradient as ONE slab: the flat buffer of data parallelism.
+        self.grad_clip = grad_clip_norm_of(cfg)
+        if self.world_size > 1 or self.grad_clip is not None:
             self.G_flat = torch.zeros(self.arena.n, device=device)          # all-reduce buffer
             self.seg_ones = torch.ones(self.arena.n // 64, dtype=torch.int16, device=device)
+        if self.grad_clip is not None:
+            n_opt = len(OPT_NAMES)
+            # per optimizer: {norm, scale} of its last step; the count of its steps with scale < 1 (a buffer of their
+            # own: read back with losses() only when the key is set); the norm kernel's partials and arrival ticket
+            self.clip_stats = torch.zeros(n_opt, 2, device=device)
+            self.clip_counts = torch.zeros(n_opt, dtype=torch.int32, device=device)
+            self.clip_partial = torch.zeros(n_opt, ops.GRAD_NORM_PARTS, dtype=torch.float64, device=device)
+            self.clip_ticket = torch.zeros(n_opt, dtype=torch.int32, device=device)
+        self._clip_host = None                # the counts as losses() read them; None once a step has been launched since
+        if self.world_size > 1:
             import torch.distributed as dist
             self.comm_stream = torch.cuda.Stream(device=device)
             torch.cuda.current_stream().synchronize()
@@ -858,6 +871,9 @@ class StepEngine:
         P.ticket = torch.zeros(1, dtype=torch.int32, device=dev)      # arrival counter of the in-kernel loss sums
         P.seg = {n: torch.zeros(self.arena.n // 64, dtype=torch.int16, device=dev) for n in OPT_NAMES}
         P.max_slab = {n: 0 for n in OPT_NAMES}
+        if self.grad_clip is not None and self.world_size == 1:
+            # min(seg, 1): the flat gradient's slab table -- an element without a gradient stays skipped, as in `seg`
+            P.seg1 = {n: torch.zeros(self.arena.n // 64, dtype=torch.int16, device=dev) for n in OPT_NAMES}
         P.cross_ok = {"CD": False, "DE": False}     # whether the split update of that boundary is legal (`_cross`)
         P.graphs = {}
         self.plans[b] = P
@@ -872,8 +888,13 @@ class StepEngine:
         ``("adam", launch)`` item for ``schedule.lockstep``."""
         o = self.opts[name]
         assert part is not None or not early
+        clip = self.grad_clip is not None
+        # (the norm needs the optimizer's whole range complete, and one scale for all of it: no halves, no riding)
+        assert not clip or (part is None and not ride and not early)
         if notes_host is not None:
             P.seg[name].copy_(torch.from_numpy(notes_host))
+            if clip and self.world_size == 1:
+                P.seg1[name].copy_(torch.from_numpy(np.minimum(notes_host, 1)))
             if not early:       # (an early half sees only its own network's counts: `_cross`)
                 P.max_slab[name] = int(notes_host.max())      # host-side hint for the Adam kernel's lane split
         self.join_side_streams()
@@ -886,19 +907,37 @@ class StepEngine:
             n = hi - lo
             assert n > 0 and lo % 64 == 0 and n % 64 == 0 and self.world_size == 1
         m, v = o.m[lo - o.lo:], o.v[lo - o.lo:]
+        scale = None
         if self.world_size > 1:
             # flat gradient -> RCCL mean over ranks -> Adam on the averaged single slab
             ops.slab_reduce(self.G[0, lo:], self.arena.n, P.seg[name][lo // 64:], n, self.G_flat[lo:], P.max_slab[name])
             self._collective(self.G_flat[lo:o.hi])
             g, seg, max_slab = self.G_flat[lo:], self.seg_ones[lo // 64:], 1
+        elif clip:
+            # one GPU with `grad_clip_norm`: the same flat gradient (slab_reduce sums the slabs in the order the update
+            # kernel of this slab hint does).  The update then reads it as one slab through min(seg, 1) -- elements
+            # without a gradient stay skipped -- and KEEPS the plain path's slab hint, i.e. its kernel form (the forms
+            # differ in one contracted multiply-add): with a scale of exactly 1 the step is bit
+            # for bit the unclipped one.
+            ops.slab_reduce(self.G[0, lo:], self.arena.n, P.seg[name][lo // 64:], n, self.G_flat[lo:], P.max_slab[name])
+            g, seg, max_slab = self.G_flat[lo:], P.seg1[name][lo // 64:], P.max_slab[name]
         else:
             g, seg, max_slab = self.G[0, lo:], P.seg[name][lo // 64:], P.max_slab[name]
+        if clip:
+            # {norm, scale} of the (rank-averaged) flat gradient: every rank computes the same numbers
+            i = o.index
+            scale = self.clip_stats[i, 1:2]
+            ops.grad_norm(g, self.arena.n, seg, n, 1, self.grad_clip, self.clip_partial[i], self.clip_ticket[i:i + 1],
+                          self.clip_stats[i], self.clip_counts[i:i + 1])
         if early and notes_host is not None:
             max_slab = max(max_slab, int(notes_host[lo // 64:(lo + n) // 64].max()))
         nan = self.nan_flags[o.index:o.index + 1] if self.detect_anomaly else None
 
         def launch():
-            if self.detect_anomaly:     # the same update by the checked twins of its kernels (all four rules)
+            if clip:                    # the update with the gradient times the scale (checked or not, all four rules)
+                ops.optim_step_clip(self.arena.P[lo:], m, v, g, self.arena.n, seg, n, o.rule, o.hyper,
+                                    self.steps_dev[o.index:], max_slab, nan_step=nan, scale=scale)
+            elif self.detect_anomaly:   # the same update by the checked twins of its kernels (all four rules)
                 ops.optim_step(self.arena.P[lo:], m, v, g, self.arena.n, seg, n, o.rule, o.hyper,
                                self.steps_dev[o.index:], max_slab, nan_step=nan)
             elif o.rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW):
@@ -1078,8 +1117,10 @@ class StepEngine:
         across = c.get("pair_across_phases", True)
         across = set(across) if isinstance(across, (list, tuple, set)) else ({"AB", "CD", "DE"} if across else set())
         assert across <= {"AB", "CD", "DE"}, across
+        # (`grad_clip_norm`: an optimizer's norm launch needs its whole gradient, and both halves of an update one scale:
+        # no split, no co-launched update -- the phases end as they do without `pair_across_phases`)
         crossable = (pair and self.world_size == 1 and self.phase_hook is None and self.post_phase_hook is None and
-                     hasattr(enc, "backward_steps") and hasattr(dec, "backward_steps"))
+                     self.grad_clip is None and hasattr(enc, "backward_steps") and hasattr(dec, "backward_steps"))
         if not pair:
             with self.aux_branch():
                 dec.forward(D, styles, P.m_dec[0])
@@ -1182,6 +1223,7 @@ class StepEngine:
                              f"torch.Size([{b}, {self.nstyle}])")
         P = self.plan(b)
         self._nan_host = None
+        self._clip_host = None
         stride = self.cursor_stride if self.cursor_stride is not None else b
         if self._host_cursor + b > len(self.train_spec):
             raise RuntimeError(f"epoch exhausted: rows [{self._host_cursor}, {self._host_cursor + b}) exceed the "
@@ -1369,7 +1411,18 @@ class StepEngine:
         words = self._epoch_words.cpu()       # the loss slots and the NaN flag words: one readback
         self._nan_host = words[8:8 + len(OPT_NAMES)].tolist()
         v = words[:8].view(torch.float32).tolist()
+        if self.grad_clip is not None:        # (only with the key set: the counts of clipped steps)
+            self._clip_host = self.clip_counts.tolist()
         return {k: v[i] for k, i in LOSS_SLOTS.items()}
+
+    @_on_stream
+    def clipped_steps(self):
+        """``grad_clip_norm``: per optimizer (``OPT_NAMES`` order) the number of its steps so far whose gradient was
+        scaled down, ``None`` with the key absent.  Uses what the last ``losses()`` read when no step has been launched
+        since; otherwise reads the counters now."""
+        if self.grad_clip is None:
+            return None
+        return list(self._clip_host) if self._clip_host is not None else self.clip_counts.tolist()
 
     def _state_buffers(self):
         """Every module buffer of encoder, decoder and discriminator, in ``named_buffers()`` order."""
@@ -1390,7 +1443,10 @@ class StepEngine:
         torch.cuda.current_stream().synchronize()
         opts = [self.opts[n] for n in OPT_NAMES]
         bns = self.enc.bn_modules + self.dec.bn_modules
-        return {"arena": self.arena.P.cpu(),
+        # (`grad_clip_norm`: the counts of clipped steps travel too; without the key the dict is what it was)
+        clip = {"clip_counts": self.clip_counts.cpu()} if self.grad_clip is not None else {}
+        return {**clip,
+                "arena": self.arena.P.cpu(),
                 "buffers": [b_.cpu() for b_ in self._state_buffers()],
                 "bn_counts": [int(self.bn_counts.get(id(bn), 0)) for bn in bns],
                 "opt_m": [o.m.cpu() for o in opts], "opt_v": [o.v.cpu() for o in opts],
@@ -1411,6 +1467,10 @@ class StepEngine:
                   (self.rng_state, state["rng_state"]), (self.nan_flags, state["nan_flags"])] +
                  list(zip(bufs, state["buffers"])) +
                  [(o.m, t) for o, t in zip(opts, state["opt_m"])] + [(o.v, t) for o, t in zip(opts, state["opt_v"])])
+        if (self.grad_clip is not None) != ("clip_counts" in state):
+            raise ValueError("StepEngine.load_state: the state was taken from an engine of another configuration")
+        if self.grad_clip is not None:
+            pairs.append((self.clip_counts, state["clip_counts"]))
         if (len(state["buffers"]) != len(bufs) or len(state["bn_counts"]) != len(bns) or
                 any(len(state[k]) != len(opts) for k in ("opt_m", "opt_v", "opt_lr", "opt_base_lr")) or
                 any(mine.shape != saved.shape or mine.dtype != saved.dtype for mine, saved in pairs)):
@@ -1423,6 +1483,7 @@ class StepEngine:
         self.bn_counts = {id(bn): int(n) for bn, n in zip(bns, state["bn_counts"])}
         self.seed = int(state["seed"])
         self._nan_host = None
+        self._clip_host = None
         torch.cuda.current_stream().synchronize()      # the host tensors of `state` may go once this returns
 
     @_on_stream

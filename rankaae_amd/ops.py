@@ -370,6 +370,40 @@ def optim_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, m
     _probed(family, 28 * n, launch, tag=OPT_RULE_NAMES[rule])
 
 
+def optim_step_clip(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab=512, nan_step=None,
+                    scale=None):
+    """``raae_optim_step_clip``: ``optim_step`` with the gradient multiplied by the device float ``scale[0]`` (the clip
+    scale ``grad_norm`` leaves) before weight decay and the moments.  ``scale=None``: exactly ``optim_step``."""
+    if rule not in OPT_RULE_NAMES:
+        raise ValueError(f"unknown optimizer rule {rule!r}")
+    if hyper.numel() < (5 if rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW) else 8):       # what the kernel reads
+        raise ValueError(f"{OPT_RULE_NAMES[rule]}: hyper holds {hyper.numel()} values, the rule reads 8")
+    family = "adam_kernel" if rule in (_lib.OPT_ADAM, _lib.OPT_ADAMW) else "optim_kernel"
+
+    def launch():
+        check(_lib.load().raae_optim_step_clip(_ptr(p), _ptr(m), _ptr(v), _ptr(g_slabs), slab_stride,
+                                               _ptr(seg_nslab, torch.int16), n, int(rule), _ptr(hyper, torch.float64),
+                                               _ptr(step, torch.int32), int(max_nslab),
+                                               _ptr(nan_step, torch.int32) if nan_step is not None else None,
+                                               _ptr(scale) if scale is not None else None, _stream()),
+              "raae_optim_step_clip")
+    _probed(family, 28 * n, launch, tag=OPT_RULE_NAMES[rule])
+
+
+GRAD_NORM_PARTS = 256       # RAAE_GRAD_NORM_PARTS
+
+
+def grad_norm(g_slabs, slab_stride, seg_nslab, n, max_nslab, max_norm, partial, ticket, out, clipped):
+    """``raae_grad_norm``: ``out`` (2 floats) = {L2 norm of the slab-summed gradient, min(1, max_norm / (norm + 1e-6))};
+    ``clipped`` (int32 word) += 1 when the scale is below 1.  ``partial``: ``GRAD_NORM_PARTS`` doubles, ``ticket``: an
+    int32 word that is zero before the first launch (the launch leaves it zero)."""
+    if partial.numel() < GRAD_NORM_PARTS or out.numel() < 2:
+        raise ValueError("grad_norm: partial holds GRAD_NORM_PARTS doubles, out two floats")
+    check(_lib.load().raae_grad_norm(_ptr(g_slabs), slab_stride, _ptr(seg_nslab, torch.int16), n, int(max_nslab),
+                                     float(max_norm), _ptr(partial, torch.float64), _ptr(ticket, torch.int32), _ptr(out),
+                                     _ptr(clipped, torch.int32), _stream()), "raae_grad_norm")
+
+
 def slab_reduce(g_slabs, slab_stride, seg_nslab, n, out, max_nslab=512):
     check(_lib.load().raae_slab_reduce(_ptr(g_slabs), slab_stride, _ptr(seg_nslab, torch.int16), n, _ptr(out),
                                        int(max_nslab), _stream()), "raae_slab_reduce")

@@ -28,6 +28,19 @@ def check_optimizer(cfg):
                     raise ValueError(f"{name}: invalid learning rate {lr!r} ({key} * lr_base); {name} needs lr > 0")
 
 
+def grad_clip_norm_of(cfg):
+    """Build-only key ``grad_clip_norm`` (default absent / ``null``: off): a finite float > 0.  Each of the five
+    optimizers then multiplies its gradient by ``min(1, grad_clip_norm / (norm + 1e-6))`` before its update, ``norm``
+    being the L2 norm of that optimizer's own gradient -- ``torch.nn.utils.clip_grad_norm_`` over the optimizer's
+    parameters.  Returns the float, or None."""
+    value = cfg.get("grad_clip_norm")
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < float("inf")):
+        raise ValueError(f"grad_clip_norm must be absent, null or a finite number > 0, not {value!r}")
+    return float(value)
+
+
 def detect_anomaly_on(cfg):
     """Build-only key ``detect_anomaly`` (default ``true``: the reference turns on
     ``torch.autograd.set_detect_anomaly(True)`` at import, sc/clustering/trainer.py:11).  On, the optimizer updates

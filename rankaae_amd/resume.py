@@ -101,6 +101,10 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     keys = set(FINGERPRINT_KEYS) | {k for k in cfg if k.startswith("alpha_") or k.startswith("lr_ratio_") or "dropout" in k}
     fp = {f"cfg.{k}": cfg.get(k) for k in sorted(keys)}
     fp = {k: (v if isinstance(v, (bool, int, float, str, type(None))) else repr(v)) for k, v in fp.items()}
+    # `grad_clip_norm` shapes the step as well; absent and null are the same run (and the same entry-less fingerprint
+    # as a file written before the key existed)
+    if cfg.get("grad_clip_norm") is not None:
+        fp["cfg.grad_clip_norm"] = float(cfg["grad_clip_norm"])
     spec = np.asarray(train_spec, dtype=np.float64)
     fp.update({"tile_rows_mult": int(tile_mult), "arena.n": int(arena_n), "rows.train": int(n_train),
                "rows.val": int(n_val), "spectra.sum": float(spec.sum()), "spectra.sum_sq": float((spec * spec).sum())})

@@ -31,9 +31,10 @@ import numpy as np
 import torch
 
 from .dataloader import get_dataloaders
-from .engine import StepEngine
+from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
-from .parameter import Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, resume_on
+from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, grad_clip_norm_of,
+                        resume_on)
 from . import resume as resume_file
 
 
@@ -123,6 +124,7 @@ class Trainer:
                              "(SURVEY.md finding 4)")
         cfg = config_parameters.to_dict()
         check_optimizer(cfg)        # before anything touches the GPU
+        self.grad_clip_norm = grad_clip_norm_of(cfg)
         self.detect_anomaly = detect_anomaly_on(cfg)
         # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
         # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
@@ -366,6 +368,7 @@ class Trainer:
         # (the collector is held off once plans and captured graphs exist: after the second epoch of a run from
         # scratch, after the first one of a resumed run)
         freeze_epoch = 1 if first_epoch == 0 else first_epoch
+        clipped_before = eng.clipped_steps()        # (None without `grad_clip_norm`; a resumed run: the restored counts)
         for epoch in range(first_epoch, self.max_epoch):
             alpha_ = alpha(epoch / self.max_epoch, self.alpha_flat_step, self.alpha_limit)
             perm = broadcast_tensor_from_rank0(self.train_loader.epoch_permutation(), self.device, self.pg)
@@ -395,6 +398,15 @@ class Trainer:
                         self._write_resume(epoch, None, best_combined_metric, best_chpt_file, finished=True,
                                            error=(nan[0], nan[1], epoch))
                     raise AnomalyError(nan[0], nan[1], epoch)
+            if self.grad_clip_norm is not None:
+                # (read by losses(), like the anomaly flags; the counters run over the whole training)
+                clipped = eng.clipped_steps()
+                steps = [n_batch if (name != "smoothness" or smooth) else 0 for name in OPT_NAMES]
+                if lead:
+                    self.logger.info(f"Epoch {epoch}: grad_clip_norm {self.grad_clip_norm:g}: " + ", ".join(
+                        f"{name} clipped {k - k0} of {n} steps"
+                        for name, k, k0, n in zip(OPT_NAMES, clipped, clipped_before, steps)))
+                clipped_before = clipped
             if not smooth:
                 tl["smooth"] = 0.0
             if self.world > 1:

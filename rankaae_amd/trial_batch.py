@@ -59,6 +59,8 @@ class TrialBatch:
                 raise ValueError("the engines of a TrialBatch must share one HIP stream (StepEngine(..., stream=s))")
             if e.aux_missing != e0.aux_missing:
                 raise ValueError("the engines of a TrialBatch must agree on whether their data has missing descriptors")
+            if e.grad_clip != e0.grad_clip:
+                raise ValueError("the engines of a TrialBatch must agree on grad_clip_norm")
             if not e.cfg.get("fused_step_begin", True) or not e.cfg.get("fused_discriminator", True):
                 raise ValueError("a TrialBatch needs the fused step head and the fused discriminator")
         self.engines, self.stream, self.T = list(engines), e0.stream, len(engines)
