@@ -365,6 +365,19 @@ int raae_grad_norm(const float* g_slabs, long slab_stride, const unsigned short*
 int raae_optim_step_clip(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
                          const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
                          int max_nslab, int* nan_step, const float* scale, void* stream);
+/* ---- moving average of the weights (ABI 27; config key `ema_decay`) ----
+ * raae_ema_step: for i in [0, n):  ema[i] = fmaf(d, ema[i], omd * p[i]),  d = (float)decay, omd = (float)(1.0 - decay),
+ * both formed on the host, once.  Plain fp32 -- the product is rounded, then one fused multiply-add -- no atomics and no
+ * reduction: a graph replay is bit for bit the eager call, and every element sees the same three operations whichever
+ * body handles it.  One element-wise pass: float4 loads and stores when ema and p are both 16-byte aligned (and a
+ * scalar tail for n % 4), one float per load otherwise; the grid is sized from n (four elements per thread) and capped
+ * at 64 workgroups, above which the kernel grid-strides.  Elements outside [0, n) are not touched.  ema and p must not
+ * overlap.  A NaN in p[i] makes ema[i] NaN (it is not hidden), an Inf makes it Inf or NaN.
+ *   decay: 0 <= decay < 1 (0: ema = p); n >= 1.  Anything else, a NaN decay or a NULL pointer: RAAE_EINVAL, nothing is
+ *   launched and nothing written.
+ * Has the batched form (raae_record_* / raae_multi_*): plane z reads its own {ema, p, n, d, omd}, so the trials of a
+ * batch may differ in decay. */
+int raae_ema_step(float* ema, const float* p, long n, double decay, void* stream);
 /* ====================== 1-D convolutional networks (ae_form: compact) ======================
  * Activations are [B][C][L] fp32, stored RAW (pre-activation); what a consumer sees is a *view*:
  *     value = mask * BatchNorm( PReLU(raw, slope_c) )          (each stage optional)
@@ -616,7 +629,7 @@ int raae_step_begin(const raae_step_begin_t* p, void* stream);
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, and since ABI 26 raae_slab_reduce) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, and raae_ema_step) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -661,7 +674,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 26
+#define RAAE_ABI_VERSION 27
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

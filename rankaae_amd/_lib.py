@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librankaae_hip.so")
 
 RAAE_MAX_PARTS = 512
-ABI_VERSION = 26
+ABI_VERSION = 27
 IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP = 0, 1, 2
 OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS, OUT_RELU = 0, 1, 2, 3, 4
 G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU = 0, 1, 2, 3, 4
@@ -229,6 +229,7 @@ SIGNATURES = {
     "raae_optim_step_chk": (_I, [_P, _P, _P, _P, _L, _P, _L, _I, _P, _P, _I, _P, _P]),
     "raae_optim_step_clip": (_I, [_P, _P, _P, _P, _L, _P, _L, _I, _P, _P, _I, _P, _P, _P]),
     "raae_grad_norm": (_I, [_P, _L, _P, _L, _I, C.c_double, _P, _P, _P, _P, _P]),
+    "raae_ema_step": (_I, [_P, _P, _L, C.c_double, _P]),
     "raae_conv_fwd": (_I, [_PV, _I, _PC, _P, _P, _P, _I, _P, _P, _PI, _I, _P]),
     "raae_conv_bwd_data": (_I, [_PG, _I, _PC, _P, _PV, _P, _I, _P, _PI, _P]),
     "raae_conv_bwd_weight": (_I, [_PG, _I, _PC, _PV, _P, _P, _P, _L, _PI, _P]),

@@ -4,8 +4,10 @@
 on the validation split on the GPU, the trials are ranked and the best one is written out.
 
 Config keys: ``data_file`` (searched in ``work_dir`` if absent), ``n_aux``, ``output_name``, ``top_n``, ``n_sampling``,
-optional ``plot_job`` (skip the ranking, report that job) and ``gpu`` (device index, default 0; the evaluation has no
-CPU path).  Files, all in ``work_dir``:
+optional ``plot_job`` (skip the ranking, report that job), ``gpu`` (device index, default 0; the evaluation has no
+CPU path) and ``report_weights`` (``final``, the default, or ``ema``: evaluate every ``training/job_*/final_ema.pt``, the
+moving average of the weights that a run with ``ema_decay`` writes, instead of ``final.pt``; a job directory without
+one is a ``FileNotFoundError``, any other value a ``ValueError``).  Files, all in ``work_dir``:
 
 * ``<output_name>_model_evaluation.pkl``  every job's result dict (with ``Input`` / ``Output``), ``Rank`` and ``Score``
 * ``<output_name>.json``                  the ``top_n`` best jobs in rank order, without the spectra
@@ -27,7 +29,7 @@ import torch
 from rankaae_amd import report
 from rankaae_amd.dataloader import AuxSpectraDataset, load_csv, split_counts
 from rankaae_amd.export import Reconstruct, spectra_variation
-from rankaae_amd.parameter import Parameters
+from rankaae_amd.parameter import Parameters, report_weights_of
 
 
 def validation_split(csv_fn, n_aux):
@@ -109,6 +111,7 @@ def main(argv=None):
     args = parser.parse_args(argv)
     work_dir = os.path.abspath(os.path.expanduser(args.work_dir))
     config = Parameters.from_yaml(os.path.join(work_dir, args.config))
+    weights = report_weights_of(config)     # before anything touches the GPU
     jobs_dir = os.path.join(work_dir, "training")
     if not torch.cuda.is_available():
         raise RuntimeError("sc_generate_report evaluates the models on the HIP engine: it needs an MI355X")
@@ -129,7 +132,7 @@ def main(argv=None):
         best = str(plot_job)
         png = os.path.join(work_dir, f"{name}_{best}.png")
     else:
-        results = report.evaluate_all_models(jobs_dir, test_ds, device=device)
+        results = report.evaluate_all_models(jobs_dir, test_ds, device=device, weights=weights)
         details = {}
         results, ranked = report.sort_all_models(results, sort_score=report.sorting_algorithm, ascending=False,
                                                  top_n=config.top_n, details=details)
@@ -141,7 +144,7 @@ def main(argv=None):
         png = os.path.join(work_dir, f"{name}_best_model.png")
 
     # the best model: its own result, the latent-space export and the per-style sweeps, on one engine
-    eng = report.engine_from_model(report.load_model(jobs_dir, best), test_ds, device)
+    eng = report.engine_from_model(report.load_model(jobs_dir, best, weights), test_ds, device)
     result = report.evaluate_model(test_ds, eng)
     recon = Reconstruct(device=device, name=name)
     styles = recon.evaluate(test_ds, eng, path_to_save=work_dir)["styles"]

@@ -440,6 +440,40 @@ __global__ __launch_bounds__(256) void grad_norm_wide_kernel_m(const GradNormArg
     grad_norm_body<true>(a);
 }
 
+// ---- moving average of the weights (config key `ema_decay`): ema[i] = fmaf(d, ema[i], omd * p[i]) ----
+// One element-wise pass, plain fp32: the product omd * p[i] is rounded once and feeds the fused multiply-add (an fma
+// argument cannot be contracted further), so the vector body, the scalar body and the tail give the same bits.  No
+// atomics, no reduction: a replay is bitwise the eager call.  With both pointers 16-byte aligned a thread takes four
+// elements per load (float4) and threads 0 .. n % 4 - 1 of workgroup 0 take the tail; otherwise one element per load.
+// The choice is made HERE, from the pointers of the plane's own argument row, so every trial of a batch launches the
+// same kernel instance with the same grid (raae_multi_build compares both).
+struct EmaArgs { float* ema; const float* p; long n; float d; float omd; };
+__device__ __forceinline__ void ema_body(const EmaArgs& a) {
+    const long nthreads = (long)gridDim.x * 256, t0 = (long)blockIdx.x * 256 + threadIdx.x;
+    const float d = a.d, omd = a.omd;
+    if ((((uintptr_t)a.ema | (uintptr_t)a.p) & 15) == 0) {
+        const long nq = a.n >> 2;
+        float4* e4 = reinterpret_cast<float4*>(a.ema);
+        const float4* p4 = reinterpret_cast<const float4*>(a.p);
+        for (long q = t0; q < nq; q += nthreads) {
+            float4 e = e4[q];
+            const float4 w = p4[q];
+            e.x = fmaf(d, e.x, omd * w.x); e.y = fmaf(d, e.y, omd * w.y);
+            e.z = fmaf(d, e.z, omd * w.z); e.w = fmaf(d, e.w, omd * w.w);
+            e4[q] = e;
+        }
+        const long i = (nq << 2) + t0;          // the tail: t0 < n % 4 <= 3, i.e. workgroup 0's first threads
+        if (i < a.n) a.ema[i] = fmaf(d, a.ema[i], omd * a.p[i]);
+    } else {
+        for (long i = t0; i < a.n; i += nthreads) a.ema[i] = fmaf(d, a.ema[i], omd * a.p[i]);
+    }
+}
+__global__ __launch_bounds__(256) void ema_kernel(EmaArgs a) { ema_body(a); }
+__global__ __launch_bounds__(256) void ema_kernel_m(const EmaArgs* t) {
+    const EmaArgs a = t[blockIdx.z];
+    ema_body(a);
+}
+
 __global__ void tick_kernel(int* steps, int n, unsigned mask, unsigned long long* rng_counter, int* cursor,
                             int cursor_inc) {
     if (blockIdx.x == 0 && threadIdx.x == 0) {
@@ -711,6 +745,17 @@ extern "C" int raae_grad_norm(const float* g_slabs, long slab_stride, const unsi
     if (g > GRAD_NORM_PARTS) g = GRAD_NORM_PARTS;                   // ... over at most as many workgroups as `partial` holds
     if (max_nslab > 16) raae::launch(grad_norm_wide_kernel, grad_norm_wide_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
     else raae::launch(grad_norm_kernel, grad_norm_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_ema_step(float* ema, const float* p, long n, double decay, void* stream) {
+    RAAE_CHECK_ARG(ema && p && n >= 1 && decay >= 0.0 && decay < 1.0);      // (false for a NaN decay)
+    const EmaArgs a = {ema, p, n, (float)decay, (float)(1.0 - decay)};
+    // sized for four elements per thread whatever the alignment (one geometry per n: trials of a batch agree), at most
+    // 64 workgroups -- the arena is a few tens of thousands of floats; above 65536 elements the kernel grid-strides
+    long g = ((n + 3) / 4 + 255) / 256;
+    if (g > 64) g = 64;
+    raae::launch(ema_kernel, ema_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
     RAAE_LAUNCH_RET();
 }
 

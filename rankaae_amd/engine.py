@@ -26,7 +26,7 @@ from torch import nn
 from . import _lib, ops, schedule
 from .metrics import StyleMetrics
 from .schedule import Pass
-from .parameter import check_optimizer, detect_anomaly_on, grad_clip_norm_of
+from .parameter import check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -466,6 +466,10 @@ class StepEngine:
         holds the same parameters, steps its own shard of the global batch (per-replica BatchNorm
         statistics, rank loss over the local pairs) and the five per-phase gradient arenas are averaged
         with one all-reduce each.  ``torch.distributed`` must already be initialised."""
+        # build-only key `ema_decay` (default absent: off), checked before anything touches the GPU: the engine keeps a
+        # moving average of the parameter arena, `ema_P`, advanced by one launch at the end of every step (`emit_step`)
+        self.ema_decay = ema_decay_of(cfg)
+        self.ema_P = self._ema_scratch = None
         if not torch.cuda.is_available():
             raise RuntimeError("rankaae_amd.engine needs an MI355X (no CPU/PyTorch fallback for the training path)")
         _lib.load()
@@ -532,6 +536,12 @@ class StepEngine:
                 # that skipped it would leave the others waiting in the collective
                 ok = ar.self_test() if ar is not None else agree(False, device, self.pg)
                 self.graph_ar = ar if ok else None
+        if self.ema_decay is not None:
+            # the average starts at the initial weights, once they are final (data parallel: rank 0's, broadcast above,
+            # so every rank starts from the same average; identical parameters after every update keep it identical
+            # without a collective)
+            self.ema_P = self.arena.P.detach().clone()
+            self._ema_scratch = torch.empty_like(self.ema_P)      # where `ema_weights()` parks the live weights
         from .nets_conv import CompactNet   # local import: conv emitters live in their own module
         # build-only key `precision`: "fp32" (default, the reference's arithmetic and storage) | "bf16" (hidden
         # activations and dropout multipliers stored as bf16, everything else fp32: BASELINE configs[4])
@@ -811,6 +821,7 @@ class StepEngine:
         self.side_streams, self.aux_stream = [], None
         self.G = None
         self.tape = None
+        self.ema_P = self._ema_scratch = None
 
     def __del__(self):
         # the cyclic collector runs this at an arbitrary allocation point, possibly inside ANOTHER engine's capture
@@ -1208,6 +1219,10 @@ class StepEngine:
             ops.smooth_loss_fwd_bwd(out, b, self.L, self.taps, P.lpart, P.dout, fin=(1.0, lo, 4, -1, P.ticket))
             dec.backward(D, styles, P.m_dec[3], P.dout, None)
             self._adam(P, "smoothness", self._slab_notes)
+        if self.ema_decay is not None:
+            # `ema_decay`: the moving average follows the step's last update (phase E's, or phase D's without the
+            # smoothness phase) on the main chain -- every side stream was joined before that update
+            ops.ema_step(self.ema_P, self.arena.P, self.arena.n, self.ema_decay)
         self._slab_notes = None
 
     @_on_stream
@@ -1424,6 +1439,37 @@ class StepEngine:
             return None
         return list(self._clip_host) if self._clip_host is not None else self.clip_counts.tolist()
 
+    def ema_weights(self):
+        """``with engine.ema_weights():`` -- the moving average of the weights (``ema_decay``) where the kernels read the
+        weights.  On entry the engine's stream is synchronised, ``arena.P`` is copied to a scratch arena and ``ema_P``
+        to ``arena.P`` (device copies); on exit, also when the body raises, ``arena.P`` is restored from the scratch.
+        The parameters of the modules are views of the arena and captured graphs hold its address: inside the context
+        ``validate``, ``reconstruct``, ``decode`` and a ``final.pt``-style export see the averaged weights, and nothing
+        is captured again.  BatchNorm running statistics are NOT averaged: the eval forwards use the live modules'
+        buffers.  Not for training steps (they would update the average in place of the weights).  ``RuntimeError``
+        during a graph capture and on an engine without ``ema_decay``."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            if self.ema_decay is None or self.ema_P is None:
+                raise RuntimeError("ema_weights(): this engine keeps no moving average (config key ema_decay)")
+            if self._capture is not None:
+                raise RuntimeError("ema_weights() inside a graph capture")
+            P, scratch = self.arena.P.detach(), self._ema_scratch
+            self.stream.synchronize()
+            with torch.cuda.stream(self.stream):
+                scratch.copy_(P)
+                P.copy_(self.ema_P)
+            self.stream.synchronize()       # (readers on other streams -- a module export, say -- see the average)
+            try:
+                yield self
+            finally:
+                with torch.cuda.stream(self.stream):
+                    P.copy_(scratch)
+                self.stream.synchronize()
+        return ctx()
+
     def _state_buffers(self):
         """Every module buffer of encoder, decoder and discriminator, in ``named_buffers()`` order."""
         return [b_ for mod in (self.enc_mod, self.dec_mod, self.dis_mod) for _, b_ in mod.named_buffers()]
@@ -1445,6 +1491,8 @@ class StepEngine:
         bns = self.enc.bn_modules + self.dec.bn_modules
         # (`grad_clip_norm`: the counts of clipped steps travel too; without the key the dict is what it was)
         clip = {"clip_counts": self.clip_counts.cpu()} if self.grad_clip is not None else {}
+        if self.ema_decay is not None:        # (`ema_decay`: the moving average of the arena)
+            clip["ema"] = self.ema_P.cpu()
         return {**clip,
                 "arena": self.arena.P.cpu(),
                 "buffers": [b_.cpu() for b_ in self._state_buffers()],
@@ -1471,6 +1519,10 @@ class StepEngine:
             raise ValueError("StepEngine.load_state: the state was taken from an engine of another configuration")
         if self.grad_clip is not None:
             pairs.append((self.clip_counts, state["clip_counts"]))
+        if (self.ema_decay is not None) != ("ema" in state):
+            raise ValueError("StepEngine.load_state: the state was taken from an engine of another configuration")
+        if self.ema_decay is not None:
+            pairs.append((self.ema_P, state["ema"]))
         if (len(state["buffers"]) != len(bufs) or len(state["bn_counts"]) != len(bns) or
                 any(len(state[k]) != len(opts) for k in ("opt_m", "opt_v", "opt_lr", "opt_base_lr")) or
                 any(mine.shape != saved.shape or mine.dtype != saved.dtype for mine, saved in pairs)):

@@ -404,6 +404,12 @@ def grad_norm(g_slabs, slab_stride, seg_nslab, n, max_nslab, max_norm, partial, 
                                      _ptr(clipped, torch.int32), _stream()), "raae_grad_norm")
 
 
+def ema_step(ema, p, n, decay):
+    """``raae_ema_step``: ``ema[i] = fmaf(d, ema[i], (1 - d) * p[i])`` for ``i < n`` in fp32, ``d = decay`` with
+    ``0 <= decay < 1`` (config key ``ema_decay``).  One element-wise launch; bitwise reproducible."""
+    check(_lib.load().raae_ema_step(_ptr(ema), _ptr(p), int(n), float(decay), _stream()), "raae_ema_step")
+
+
 def slab_reduce(g_slabs, slab_stride, seg_nslab, n, out, max_nslab=512):
     check(_lib.load().raae_slab_reduce(_ptr(g_slabs), slab_stride, _ptr(seg_nslab, torch.int16), n, _ptr(out),
                                        int(max_nslab), _stream()), "raae_slab_reduce")

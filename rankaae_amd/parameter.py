@@ -41,6 +41,30 @@ def grad_clip_norm_of(cfg):
     return float(value)
 
 
+def ema_decay_of(cfg):
+    """Build-only key ``ema_decay`` (default absent / ``null``: off): a finite float with ``0 < x < 1``.  The engine
+    then keeps an exponential moving average of the parameter arena, ``ema = x * ema + (1 - x) * p`` after the last
+    optimizer update of every step, and ``Trainer`` writes it out as ``final_ema.pt``.  Returns the float, or None."""
+    value = cfg.get("ema_decay", None)
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < 1.0):
+        raise ValueError(f"ema_decay must be absent, null or a finite number with 0 < ema_decay < 1, not {value!r}")
+    return float(value)
+
+
+REPORT_WEIGHTS = {"final": "final.pt", "ema": "final_ema.pt"}
+
+
+def report_weights_of(cfg):
+    """``generate_report``'s key ``report_weights``: ``final`` (default; every ``job_*/final.pt``) or ``ema`` (every
+    ``job_*/final_ema.pt``, the moving average a run with ``ema_decay`` writes).  Returns the value."""
+    value = cfg.get("report_weights", "final")
+    if not isinstance(value, str) or value not in REPORT_WEIGHTS:
+        raise ValueError(f"report_weights must be 'final' or 'ema', not {value!r}")
+    return value
+
+
 def detect_anomaly_on(cfg):
     """Build-only key ``detect_anomaly`` (default ``true``: the reference turns on
     ``torch.autograd.set_detect_anomaly(True)`` at import, sc/clustering/trainer.py:11).  On, the optimizer updates

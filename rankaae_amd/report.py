@@ -279,23 +279,35 @@ def list_jobs(jobs_dir):
                   if j.startswith("job_") and os.path.exists(os.path.join(jobs_dir, j, "final.pt")))
 
 
-def load_model(jobs_dir, job):
-    return torch.load(os.path.join(jobs_dir, job, "final.pt"), map_location="cpu", weights_only=False)
+def load_model(jobs_dir, job, weights="final"):
+    """The model dict of ``job``: ``final.pt``, or with ``weights="ema"`` (config key ``report_weights``) the moving
+    average ``final_ema.pt`` that a run with ``ema_decay`` writes -- ``FileNotFoundError`` naming the job directory
+    where the run wrote none."""
+    from .parameter import REPORT_WEIGHTS
+    if weights not in REPORT_WEIGHTS:
+        raise ValueError(f"report_weights must be 'final' or 'ema', not {weights!r}")
+    path = os.path.join(jobs_dir, job, REPORT_WEIGHTS[weights])
+    if weights != "final" and not os.path.exists(path):
+        raise FileNotFoundError(f"report_weights: {weights}: {os.path.join(jobs_dir, job)} has no "
+                                f"{REPORT_WEIGHTS[weights]} (was the run trained with ema_decay?)")
+    return torch.load(path, map_location="cpu", weights_only=False)
 
 
-def evaluate_all_models(jobs_dir, test_ds, device=None, batched=True, info=None):
+def evaluate_all_models(jobs_dir, test_ds, device=None, batched=True, info=None, weights="final"):
     """``analysis.evaluate_all_models`` (analysis.py:105-123): ``{job: result dict}`` for every ``job_*`` under
     ``jobs_dir``, in sorted name order.  With ``batched`` and jobs of one architecture, the J eval forwards and the J
     score sequences are replayed as one launch sequence with ``gridDim.z = J``; otherwise (or if the recorder refuses)
     one job after the other.  The numbers are the same either way: a grid plane runs the kernel body a model runs
-    alone.  ``info``: a dict that receives ``mode`` ("batched" / "sequential") and ``launches``."""
+    alone.  ``info``: a dict that receives ``mode`` ("batched" / "sequential") and ``launches``.  ``weights``: "final"
+    (``final.pt``) or "ema" (``final_ema.pt`` of every job, ``load_model``)."""
     device = device or torch.device("cuda:0")
     names = list_jobs(jobs_dir)
     if not names:
         raise FileNotFoundError(f"no job_*/final.pt under {jobs_dir}")
     stream = torch.cuda.Stream(device=device)
     stream.wait_stream(torch.cuda.current_stream(device))
-    jobs = [_Job(engine_from_model(load_model(jobs_dir, j), test_ds, device, stream=stream), test_ds) for j in names]
+    models = [load_model(jobs_dir, j, weights) for j in names]       # (before any engine exists: a missing file raises here)
+    jobs = [_Job(engine_from_model(m, test_ds, device, stream=stream), test_ds) for m in models]
     info = info if info is not None else {}
     info.update(mode="sequential", launches=0)
     with torch.cuda.stream(stream):

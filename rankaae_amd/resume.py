@@ -105,6 +105,9 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     # as a file written before the key existed)
     if cfg.get("grad_clip_norm") is not None:
         fp["cfg.grad_clip_norm"] = float(cfg["grad_clip_norm"])
+    # `ema_decay` likewise: the resume file carries the moving average, which a run with another decay would continue
+    if cfg.get("ema_decay") is not None:
+        fp["cfg.ema_decay"] = float(cfg["ema_decay"])
     spec = np.asarray(train_spec, dtype=np.float64)
     fp.update({"tile_rows_mult": int(tile_mult), "arena.n": int(arena_n), "rows.train": int(n_train),
                "rows.val": int(n_val), "spectra.sum": float(spec.sum()), "spectra.sum_sq": float((spec * spec).sum())})

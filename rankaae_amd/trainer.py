@@ -13,6 +13,8 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
                 random stream for every trial of a run, as in the reference (whose trials are independent draws)
   ``detect_anomaly`` True (default, the reference's ``set_detect_anomaly(True)``): a NaN parameter gradient ends
                 ``train()`` with ``AnomalyError`` at the end of its epoch, before anything of that epoch is logged or saved
+  ``ema_decay`` a number in (0, 1) (default absent: off): the engine keeps a moving average of the weights; after the last
+                epoch it is validated once (one ``EMA weights:`` log line) and written as ``final_ema.pt``
 
 Data parallel (the north star's replacement of the ipyparallel trial farm): started under
 ``torch.distributed.run`` (WORLD_SIZE > 1) every rank builds the same ``Trainer``; rank r steps rows
@@ -33,8 +35,8 @@ import torch
 from .dataloader import get_dataloaders
 from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
-from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, grad_clip_norm_of,
-                        resume_on)
+from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, ema_decay_of,
+                        grad_clip_norm_of, resume_on)
 from . import resume as resume_file
 
 
@@ -125,6 +127,7 @@ class Trainer:
         cfg = config_parameters.to_dict()
         check_optimizer(cfg)        # before anything touches the GPU
         self.grad_clip_norm = grad_clip_norm_of(cfg)
+        self.ema_decay = ema_decay_of(cfg)
         self.detect_anomaly = detect_anomaly_on(cfg)
         # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
         # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
@@ -442,6 +445,24 @@ class Trainer:
             torch.save(self._model_dict(), f"{self.work_dir}/final.pt")
             if best_chpt_file is not None:
                 shutil.copy2(best_chpt_file, f"{self.work_dir}/best.pt")
+        if self.ema_decay is not None:
+            # `ema_decay`: one validation with the moving average in place of the weights, and `final_ema.pt` -- the
+            # dict of `final.pt` with the averaged parameters (the BatchNorm buffers are the live modules': they are
+            # not averaged).  Everything above came from the live weights; nothing below reaches the returned metrics.
+            # (Data parallel: the validation holds collectives, so every rank runs it; rank 0 logs and writes.)
+            with eng.ema_weights():
+                _, vl = eng.validate(val_spec, val_aux)
+                style_shapiro, style_rho = eng.val_style_metrics()
+                if lead:
+                    ema_metrics = [float(np.min(style_shapiro)), vl["recon"], vl["mutual_info"],
+                                   float(np.max(np.fabs(style_rho))), vl["kendall"]]
+                    self.logger.info(
+                        f"EMA weights: decay {self.ema_decay:g}; validation losses " +
+                        ", ".join(f"{k} {vl[k]:.6f}" for k in ("adversarial", "kendall", "recon", "mutual_info", "smooth")) +
+                        "; metrics (min Shapiro W, recon, validation mutual info, max |Spearman rho|, kendall) " +
+                        ", ".join(f"{m:.6f}" for m in ema_metrics))
+                    torch.save(self._model_dict(), f"{self.work_dir}/final_ema.pt")
+        if lead:
             if self.checkpoint_every and metrics is not None:
                 # `resume` (train_sc) skips a trial whose file says so
                 self._write_resume(self.max_epoch - 1, metrics, best_combined_metric, best_chpt_file, finished=True)

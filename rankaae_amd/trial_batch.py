@@ -61,6 +61,9 @@ class TrialBatch:
                 raise ValueError("the engines of a TrialBatch must agree on whether their data has missing descriptors")
             if e.grad_clip != e0.grad_clip:
                 raise ValueError("the engines of a TrialBatch must agree on grad_clip_norm")
+            if (e.ema_decay is None) != (e0.ema_decay is None):
+                # (the value may differ: every grid plane of raae_ema_step reads its own decay)
+                raise ValueError("the engines of a TrialBatch must agree on whether ema_decay is set")
             if not e.cfg.get("fused_step_begin", True) or not e.cfg.get("fused_discriminator", True):
                 raise ValueError("a TrialBatch needs the fused step head and the fused discriminator")
         self.engines, self.stream, self.T = list(engines), e0.stream, len(engines)
