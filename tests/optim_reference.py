@@ -13,7 +13,11 @@ import torch
 
 class RAdam(torch.optim.Optimizer):
     """torch_optimizer.RAdam (0.1.0): rectified Adam (Liu et al. 2019) with decoupled weight decay, including the
-    class's 10-entry cache of ``(step, N_sma, step_size)`` keyed on ``step % 10``."""
+    class's 10-entry cache of ``(step, N_sma, step_size)`` keyed on ``step % 10``.  The original works on
+    ``.float()`` copies of the gradient and the parameter: ``compute_dtype`` (a subclass may set float64 to pin a
+    float64 reference to these very lines)."""
+
+    compute_dtype = torch.float32
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0):
         if lr <= 0.0:
@@ -34,8 +38,8 @@ class RAdam(torch.optim.Optimizer):
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                grad = p.grad.float()
-                p_fp32 = p.float()
+                grad = p.grad.to(self.compute_dtype)
+                p_fp32 = p.to(self.compute_dtype)
                 state = self.state[p]
                 if len(state) == 0:
                     state["step"] = 0
