@@ -27,6 +27,9 @@
 namespace {
 
 constexpr int kTile = 2048;
+// degree-2 fit: the share of sum u^4 below which the variance of u^2 counts as none (rounding leaves ~1e-15 of it where
+// the descriptor has two distinct values; three values, one of them on a single row of 2^20, still leave 1e-6)
+constexpr double kSelRankTol = 1e-10;
 
 struct SelArgs {
     const float* z; const double* aux; const float* sin; const float* sout; const double* th;
@@ -352,6 +355,15 @@ __device__ __forceinline__ void sel_stat_body(const A& a) {
         const double f1 = m01 / m00, f2 = m02 / m00;
         m11 -= f1 * m01; m12 -= f1 * m02; b1 -= f1 * b0;
         m22 -= f2 * m02; b2 -= f2 * b0;
+        if (m22 <= kSelRankTol * t[9]) {
+            // m22 is now n Var(u^2): none means u^2 == 1 on every row, a descriptor with two distinct values.  The basis
+            // {1, u, u^2} has rank 2 there, and Polynomial.fit's SVD answers with the minimum-norm coefficients: the line
+            // c + a1 u through the two group means, its constant shared evenly between the columns 1 and u^2.  Stated
+            // as the reduced system whose solution that is (a2 = c / 2, hence a0 = c - a2), so that the lines below --
+            // and with them every result on a full-rank column -- stay as they were.
+            m12 = 0.0; m22 = 1.0;
+            b2 = 0.5 * ((b0 - m01 * (b1 / m11)) / m00);
+        }
         const double f3 = m12 / m11;                     // (row 2, column 1) equals (1, 2) after the first step: symmetric
         m22 -= f3 * m12; b2 -= f3 * b1;
     }

@@ -96,6 +96,11 @@ def result_from_block(block, n_aux, labelled=None):
             corr[i] = {"F1 score": round(float(o[1]), 4), "CN45 Threshold": round(float(THRESH_GRID[i45]), 4),
                        "CN56 Threshold": round(float(THRESH_GRID[i56]), 4)}
         else:
+            if np.isnan(o[1]):
+                # a descriptor with one value on every (labelled) row: the kernel's slope is 0 / 0.  The reference's
+                # linregress raises there; a NaN score must not reach the ranking
+                raise ValueError(f"descriptor {i} is constant over the validation rows: cannot calculate a linear "
+                                 "regression if all x values are identical")
             corr[i] = {"Spearman": _r4(o[0]),
                        "Linear": {"slope": _r4(o[1]), "intercept": _r4(o[2]), "R2": _r4(o[3])},
                        "Quadratic": {"Parameters": np.round(o[4:7], 4).tolist(), "residue": np.round(o[7:8], 4).tolist(),
