@@ -625,11 +625,33 @@ typedef struct {
     float* tape; const int* seg_desc; const float* seg_scale; int nseg; long total;
 } raae_step_begin_t;
 int raae_step_begin(const raae_step_begin_t* p, void* stream);
+/* ---- energy-shift augmentation of the training batch (ABI 28; config key `spec_shift`) ----
+ * raae_spec_augment: called BEHIND raae_step_begin on the same state; reads rng_state = {step counter, seed, hash keys}
+ * and cursor[0] as the head published them (already advanced: nothing is added here) and writes, out of place,
+ *     spec_out[b][l] = shift(spec[idx[cursor - B + b]], l + delta_b) + z * spec_noise          b < B, l < L
+ * The draw ("Energy-shift augmentation"), every step one fp32 operation:
+ *     h_b = lowbias32(lowbias32(b + 0x80000000 + k1) ^ k2)     (k1, k2: the two hash key words at rng_state + 2)
+ *     u_b = float(h_b >> 8) * 2^-24;   delta_b = (2 u_b - 1) * s,  s = (float)max_shift    (one rounding: the product)
+ *     x = min(max(float(l) + delta_b, 0), L - 1);  i0 = floor(x);  f = x - i0 (exact);  i1 = min(i0 + 1, L - 1)
+ *     shift = in[i0] + f * (in[i1] - in[i0])       (three roundings, never fused; f == 0 gives in[i0] itself)
+ * i.e. linear interpolation with replicated edges, delta_b uniform in [-s, s).  The noise term is raae_step_begin's:
+ * z = element (noise_goff + b L + l) of the step's Gaussian numbering (Philox block (noise_goff + b L + l) >> 2 of the
+ * published counter), added by the head's expression; spec_noise == 0 adds nothing.  With max_shift == 0 the output is
+ * bit for bit what raae_step_begin writes to spec_out for the same state and spec_noise.  delta_b depends on the seed,
+ * the counter and b alone.  One element-wise launch sized by B * L (at most 1024 workgroups, grid-stride above): four
+ * samples per thread and one float4 store when L % 4 == 0 and spec_out is 16-byte aligned, one sample per thread
+ * otherwise -- the same bits either way; no LDS, no atomics, so a graph replay is bitwise the eager call.  spec and
+ * spec_out must not overlap.
+ *   B >= 1, L >= 2, max_shift finite and >= 0 (as a float), spec_noise not NaN, noise_goff >= 0 and a multiple of 4,
+ *   no NULL pointer.  Anything else: RAAE_EINVAL, nothing is launched and nothing written.
+ * Has the batched form: plane z reads its own argument block, so the trials of a batch may differ in max_shift. */
+int raae_spec_augment(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
+                      int B, int L, double max_shift, double spec_noise, long noise_goff, float* spec_out, void* stream);
 
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, and raae_ema_step) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step and raae_spec_augment) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -674,7 +696,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 27
+#define RAAE_ABI_VERSION 28
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -658,6 +658,78 @@ __global__ __launch_bounds__(256) void step_begin_kernel_m(const StepBeginArgs* 
     step_begin_body(a);
 }
 
+// ---- energy-shift augmentation (config key `spec_shift`): the batch rows resampled at l + delta_b, then the noise ----
+// Runs BEHIND the step head and reads the counter, the seed, the hash keys and the row cursor as the head published
+// them (no + 1, no + stride here).  Row b draws delta_b = (2 u_b - 1) * s, u_b = (h_b >> 8) * 2^-24 with
+// h_b = lowbias32(lowbias32(b + SPEC_SHIFT_OFF + k1) ^ k2): the step's dropout hash, at an index no tape element has.
+// Every rounding is written out and the two functions below are compiled with contraction off (a product fused into
+// the sum that follows it would skip a rounding: x = l + delta_b must see the ROUNDED delta_b), so the float4 body and
+// the scalar body give the same bits and a float64 reference can follow them: delta_b is one multiply, x = clamp(l + delta_b) one add,
+// f = x - floor(x) is exact, the interpolation a subtraction, a product and a sum.  The noise term is the head's
+// expression with the head's Gaussian numbering.  Out of place, no LDS, no atomics: a replay is bitwise.
+constexpr uint32_t SPEC_SHIFT_OFF = 0x80000000u;
+struct SpecAugArgs {
+    const float* spec; const long* idx; const int* cursor; const unsigned long long* rng_state; int B; int L;
+    float max_shift; float spec_noise; long noise_goff; float* spec_out;
+};
+__device__ __forceinline__ float spec_shift_delta(uint32_t b, uint32_t k1, uint32_t k2, float s) {
+#pragma clang fp contract(off)
+    const uint32_t h = raae::lowbias32(raae::lowbias32(b + SPEC_SHIFT_OFF + k1) ^ k2);
+    const float u = (float)(h >> 8) * (1.0f / 16777216.0f);       // exact: 24 bits
+    return (2.f * u - 1.f) * s;                                   // (2 u - 1 is exact; the product is the only rounding)
+}
+__device__ __forceinline__ float spec_shift_sample(const float* row, int l, int L, float delta) {
+#pragma clang fp contract(off)
+    const float x = fminf(fmaxf((float)l + delta, 0.f), (float)(L - 1));
+    const float fl = floorf(x);
+    const int i0 = (int)fl, i1 = min(i0 + 1, L - 1);
+    const float f = x - fl;                                       // exact (Sterbenz / x < 2^24)
+    const float v0 = row[i0];
+    // f == 0: the sample itself (v0 + 0 * (v1 - v0) would turn -0 into +0 and an Inf neighbour into NaN)
+    const float d = row[i1] - v0, p = f * d;
+    return f == 0.f ? v0 : v0 + p;
+}
+__device__ __forceinline__ void spec_augment_body(const SpecAugArgs& a) {
+    const unsigned long long ctr = a.rng_state[0], seed = a.rng_state[1];
+    const uint32_t k1 = reinterpret_cast<const unsigned*>(a.rng_state + 2)[0];
+    const uint32_t k2 = reinterpret_cast<const unsigned*>(a.rng_state + 2)[1];
+    const long* idx = a.idx + (a.cursor[0] - a.B);
+    const long nthreads = (long)gridDim.x * 256, t0 = (long)blockIdx.x * 256 + threadIdx.x;
+    const long n = (long)a.B * a.L;
+    // four samples of one row per thread and one float4 store when the rows are whole quads and spec_out is 16-byte
+    // aligned (decided HERE, per plane: the trials of a batch launch one instance with one grid); else one per thread
+    if ((a.L & 3) == 0 && ((uintptr_t)a.spec_out & 15) == 0) {
+        for (long i4 = t0; i4 * 4 < n; i4 += nthreads) {
+            const long i = i4 * 4;
+            const int b = (int)(i / a.L), l = (int)(i - (long)b * a.L);
+            const float* row = a.spec + (size_t)idx[b] * a.L;
+            const float delta = spec_shift_delta((uint32_t)b, k1, k2, a.max_shift);
+            float4 v;
+            v.x = spec_shift_sample(row, l, a.L, delta); v.y = spec_shift_sample(row, l + 1, a.L, delta);
+            v.z = spec_shift_sample(row, l + 2, a.L, delta); v.w = spec_shift_sample(row, l + 3, a.L, delta);
+            if (a.spec_noise != 0.f) {
+                float z[4];
+                normal4((a.noise_goff + i) >> 2, ctr, seed, z);
+                v.x += z[0] * a.spec_noise; v.y += z[1] * a.spec_noise; v.z += z[2] * a.spec_noise; v.w += z[3] * a.spec_noise;
+            }
+            *reinterpret_cast<float4*>(a.spec_out + i) = v;
+        }
+    } else {
+        for (long i = t0; i < n; i += nthreads) {
+            const int b = (int)(i / a.L), l = (int)(i - (long)b * a.L);
+            const float* row = a.spec + (size_t)idx[b] * a.L;
+            float v = spec_shift_sample(row, l, a.L, spec_shift_delta((uint32_t)b, k1, k2, a.max_shift));
+            if (a.spec_noise != 0.f) { float z[4]; normal4((a.noise_goff + i) >> 2, ctr, seed, z); v += z[(a.noise_goff + i) & 3] * a.spec_noise; }
+            a.spec_out[i] = v;
+        }
+    }
+}
+__global__ __launch_bounds__(256) void spec_augment_kernel(SpecAugArgs a) { spec_augment_body(a); }
+__global__ __launch_bounds__(256) void spec_augment_kernel_m(const SpecAugArgs* t) {
+    const SpecAugArgs a = t[blockIdx.z];
+    spec_augment_body(a);
+}
+
 }  // namespace
 
 extern "C" int raae_adam_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
@@ -794,6 +866,22 @@ extern "C" int raae_step_begin(const raae_step_begin_t* p, void* stream) {
     if (g > 1024) g = 1024;                 // ... up to 1024 workgroups (their tickets, ~40 us, come back during ~45 us of fill at 4096 rows)
     if (g < 64) g = 64;
     raae::launch(step_begin_kernel, step_begin_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_spec_augment(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
+                                 int B, int L, double max_shift, double spec_noise, long noise_goff, float* spec_out,
+                                 void* stream) {
+    RAAE_CHECK_ARG(spec && idx && cursor && rng_state && spec_out && B >= 1 && L >= 2);
+    const float s = (float)max_shift, sn = (float)spec_noise;
+    RAAE_CHECK_ARG(max_shift >= 0.0 && s < INFINITY && sn == sn);      // (false for a NaN or Inf max_shift)
+    RAAE_CHECK_ARG((noise_goff & 3) == 0 && noise_goff >= 0);
+    const SpecAugArgs a = {spec, idx, cursor, rng_state, B, L, s, sn, noise_goff, spec_out};
+    // sized by B * L, four elements per thread whichever body runs (one geometry per shape: trials of a batch agree),
+    // at most 1024 workgroups, above which the kernel grid-strides
+    long g = (((long)B * L + 3) / 4 + 255) / 256;
+    if (g > 1024) g = 1024;
+    raae::launch(spec_augment_kernel, spec_augment_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
     RAAE_LAUNCH_RET();
 }
 

@@ -26,7 +26,7 @@ from torch import nn
 from . import _lib, ops, schedule
 from .metrics import StyleMetrics
 from .schedule import Pass
-from .parameter import check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of
+from .parameter import check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, spec_shift_of
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -470,6 +470,9 @@ class StepEngine:
         # moving average of the parameter arena, `ema_P`, advanced by one launch at the end of every step (`emit_step`)
         self.ema_decay = ema_decay_of(cfg)
         self.ema_P = self._ema_scratch = None
+        # build-only key `spec_shift` (default absent: off), checked likewise: every training step resamples the rows of
+        # its batch at a random per-row energy shift, one launch behind the step head (`emit_step`)
+        self.spec_shift = spec_shift_of(cfg, rng_mode)
         if not torch.cuda.is_available():
             raise RuntimeError("rankaae_amd.engine needs an MI355X (no CPU/PyTorch fallback for the training path)")
         _lib.load()
@@ -870,6 +873,9 @@ class StepEngine:
         P.m_enc.append(self.enc.mask_slots(tape, b))            # phase E :191
         P.m_dec.append(self.dec.mask_slots(tape, b))
         tape.finalize(dev)
+        if self.spec_shift is not None:
+            # the shift of row b is drawn at hash index SPEC_SHIFT_OFF + b: beyond every dropout element of the step
+            assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF
         P.rank_work = torch.empty(self._rank_work_bytes(b, rows_form=self.rank_pairs_global), dtype=torch.uint8, device=dev)
         if self.rank_pairs_global:
             P.aux_all = torch.empty(self.world_size * b, self.n_aux, device=dev)
@@ -1092,7 +1098,16 @@ class StepEngine:
         if P.stride is None:
             P.stride = stride
         assert P.stride == stride, "cursor stride is baked into the captured graph of this batch size"
-        if self.fused_begin:
+        if self.spec_shift is not None:
+            # `spec_shift`: the head ticks, fills the tape, gathers `aux` and writes the rows as they are (no noise);
+            # the launch behind it overwrites `P.spec` with the rows resampled at their shifts, plus the noise -- every
+            # phase of the step reads that one augmented batch
+            ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,
+                           self.train_spec, self.train_aux, self.perm, b, self.L, self.n_aux, 0.0, None, -P.noise - 1,
+                           P.spec, P.aux, tape)
+            ops.spec_augment(self.train_spec, self.perm, self.cursor, self.rng_state, b, self.L, self.spec_shift,
+                             float(c["spec_noise"]), -P.noise - 1, P.spec)
+        elif self.fused_begin:
             # tick + tape fill + gather in ONE launch (was three: 19 us of the 256-row step)
             philox = self.rng_mode == "philox"
             ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,

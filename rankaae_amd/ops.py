@@ -410,6 +410,19 @@ def ema_step(ema, p, n, decay):
     check(_lib.load().raae_ema_step(_ptr(ema), _ptr(p), int(n), float(decay), _stream()), "raae_ema_step")
 
 
+SPEC_SHIFT_OFF = 0x80000000     # hash index of row 0's shift draw: beyond every dropout element of a step (< 2^31)
+
+
+def spec_augment(spec, idx, cursor, rng_state, B, L, max_shift, spec_noise, noise_goff, spec_out):
+    """``raae_spec_augment`` (config key ``spec_shift``): behind ``step_begin`` on the same state, ``spec_out[b]`` = row
+    ``idx[cursor - B + b]`` of ``spec`` resampled at ``l + delta_b`` (linear, replicated edges; ``delta_b`` uniform in
+    ``[-max_shift, max_shift)`` from the step's hash keys) plus the head's spectral noise.  One element-wise launch."""
+    assert rng_state.dtype == torch.int64 and rng_state.numel() >= 3 and cursor.dtype == torch.int32
+    check(_lib.load().raae_spec_augment(_ptr(spec), _ptr(idx, torch.int64), _ptr(cursor, torch.int32), _ptr(rng_state, torch.int64),
+                                        int(B), int(L), float(max_shift), float(spec_noise), int(noise_goff),
+                                        _ptr(spec_out), _stream()), "raae_spec_augment")
+
+
 def slab_reduce(g_slabs, slab_stride, seg_nslab, n, out, max_nslab=512):
     check(_lib.load().raae_slab_reduce(_ptr(g_slabs), slab_stride, _ptr(seg_nslab, torch.int16), n, _ptr(out),
                                        int(max_nslab), _stream()), "raae_slab_reduce")

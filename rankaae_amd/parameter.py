@@ -53,6 +53,25 @@ def ema_decay_of(cfg):
     return float(value)
 
 
+def spec_shift_of(cfg, rng_mode=None):
+    """Build-only key ``spec_shift`` (default absent / ``null``: off): a finite float ``s > 0``, the largest shift in
+    grid points (it may be fractional).  Every training step then resamples every row of its batch at ``l + delta``,
+    ``delta`` uniform in ``[-s, s)`` and drawn per row on the device (linear interpolation, replicated edges), before
+    the spectral noise is added; validation and every export see the rows as they are.  The draw lives in the fused
+    step head's device random state, so the key needs ``rng_mode: philox`` (``rng_mode``: what the engine was built
+    with, default: the config's) and ``fused_step_begin`` on.  Returns the float, or None."""
+    value = cfg.get("spec_shift", None)
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < float("inf")):
+        raise ValueError(f"spec_shift must be absent, null or a finite number > 0, not {value!r}")
+    if (rng_mode if rng_mode is not None else cfg.get("rng_mode", "philox")) != "philox" or \
+            not cfg.get("fused_step_begin", True):
+        # (the parity mode exists for comparisons with the reference, which has no such draw to be in parity with)
+        raise ValueError("spec_shift: device RNG with the fused step head only")
+    return float(value)
+
+
 REPORT_WEIGHTS = {"final": "final.pt", "ema": "final_ema.pt"}
 
 

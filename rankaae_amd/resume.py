@@ -108,6 +108,10 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     # `ema_decay` likewise: the resume file carries the moving average, which a run with another decay would continue
     if cfg.get("ema_decay") is not None:
         fp["cfg.ema_decay"] = float(cfg["ema_decay"])
+    # `spec_shift` likewise: a run with another largest shift would continue on differently augmented batches (the
+    # draws themselves need nothing: they come from the engine's random state, which travels)
+    if cfg.get("spec_shift") is not None:
+        fp["cfg.spec_shift"] = float(cfg["spec_shift"])
     spec = np.asarray(train_spec, dtype=np.float64)
     fp.update({"tile_rows_mult": int(tile_mult), "arena.n": int(arena_n), "rows.train": int(n_train),
                "rows.val": int(n_val), "spectra.sum": float(spec.sum()), "spectra.sum_sq": float((spec * spec).sum())})

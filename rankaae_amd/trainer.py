@@ -15,6 +15,8 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
                 ``train()`` with ``AnomalyError`` at the end of its epoch, before anything of that epoch is logged or saved
   ``ema_decay`` a number in (0, 1) (default absent: off): the engine keeps a moving average of the weights; after the last
                 epoch it is validated once (one ``EMA weights:`` log line) and written as ``final_ema.pt``
+  ``spec_shift`` a number > 0 (default absent: off): every training step resamples each row of its batch at a random energy
+                shift of up to that many grid points, on the device, before the spectral noise; validation never shifts
 
 Data parallel (the north star's replacement of the ipyparallel trial farm): started under
 ``torch.distributed.run`` (WORLD_SIZE > 1) every rank builds the same ``Trainer``; rank r steps rows
@@ -36,7 +38,7 @@ from .dataloader import get_dataloaders
 from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
 from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, ema_decay_of,
-                        grad_clip_norm_of, resume_on)
+                        grad_clip_norm_of, resume_on, spec_shift_of)
 from . import resume as resume_file
 
 
@@ -128,6 +130,7 @@ class Trainer:
         check_optimizer(cfg)        # before anything touches the GPU
         self.grad_clip_norm = grad_clip_norm_of(cfg)
         self.ema_decay = ema_decay_of(cfg)
+        self.spec_shift = spec_shift_of(cfg)
         self.detect_anomaly = detect_anomaly_on(cfg)
         # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
         # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
@@ -323,6 +326,8 @@ class Trainer:
             return list(st["metrics"])
         if lead:
             os.makedirs(chkpt_dir, exist_ok=True)
+        if lead and self.spec_shift is not None:
+            self.logger.info(f"spec_shift: rows shifted by up to ±{self.spec_shift:g} grid points")
         best_chpt_file, metrics = None, None
         if lead and self.resume:
             # rows are written every 10 epochs and the run went on after its last resume file: back to that epoch
