@@ -34,8 +34,9 @@ float64 / Python-integer reference of ``step_reference``, one launch at a time, 
   moments: 0 / (0 + eps), ``p`` must come back bit for bit.
 * NOT PINNED: the high word of the Philox block number ``qg`` (a slot of 2^34 floats); the 8-deep body of the thread
   shape beyond 16 slabs (unreachable: above 16 the 8-lane shape runs); which of the two kernel symbols of an instance
-  ran is taken from the mirror, not read back from the device; the update riding in ``co_kernel`` is run
-  at the two table pairs with a backward phase A as host, not beside a forward block.  Already held elsewhere and only
+  ran is taken from the mirror, not read back from the device; the update riding in ``co_kernel`` is run here
+  at the two table pairs with a backward phase A as host (beside a forward block, at the capped grid and as a
+  two-plane program: ``test_co_kernels_gpu.py``).  Already held elsewhere and only
   cited here: a clip scale of exactly 1.0 is bitwise the plain instance and a fixed scale meets the rule
   (``test_grad_clip_gpu.py``); kinds 1 and 2 of the tape alone (``test_dense_kernels_gpu.py``).
 
