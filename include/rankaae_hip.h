@@ -647,11 +647,47 @@ int raae_step_begin(const raae_step_begin_t* p, void* stream);
  * Has the batched form: plane z reads its own argument block, so the trials of a batch may differ in max_shift. */
 int raae_spec_augment(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
                       int B, int L, double max_shift, double spec_noise, long noise_goff, float* spec_out, void* stream);
+/* ---- resolution augmentation of the training batch (ABI 29; config key `spec_broaden`) ----
+ * raae_spec_augment2: raae_spec_augment with a Gaussian broadening in front of the shift.  Called BEHIND raae_step_begin
+ * on the same state (counter, seed, hash keys and cursor as the head published them) and writes, out of place,
+ *     spec_out[b][l] = shift(g_b, l + delta_b) + z * spec_noise,   g_b = broaden(spec[idx[cursor - B + b]], sigma_b)
+ * in the order resolution, axis, detector.  The arithmetic ("Resolution augmentation"), every
+ * line one fp32 operation, compiled with contraction off where a fused product would skip a rounding:
+ *   draw     g_b = lowbias32(lowbias32(b + 0xC0000000 + k1) ^ k2)    (k1, k2: the key words at rng_state + 2; an index
+ *            no dropout element (< 2^31) and no shift draw (0x80000000 + b, b < 2^30) has)
+ *            v_b = float(g_b >> 8) * 2^-24 (exact);   sigma_b = v_b * s,  s = (float)max_sigma   (one rounding)
+ *   radius   R = ceil(3 * s): the fp32 product rounded, then the ceiling; ONE value per launch (per plane), not per row
+ *   weights  j = -R .. R:  w_0 = 1;  j != 0:  w_j = expf(-t_j),  t_j = float(j j) * q_b,  q_b = 1 / (2 * (sigma_b sigma_b))
+ *            roundings: sigma_b sigma_b; (the doubling is exact;) the division, correctly rounded; the product
+ *            float(j j) * q_b (j j is exact); expf -- the library function, NOT the fast intrinsic (__expf)
+ *            W_b = sum_j w_j, fp32, in ascending j from 0
+ *   row      g[l] = (sum_{j=-R..R} w_j * in[clamp(l + j, 0, L - 1)]) / W_b:  acc = fmaf(w_j, in[..], acc) from acc = 0 in
+ *            ascending j -- FUSED, one rounding per tap -- then one correctly rounded division.  There is one body.
+ *   sigma_b == 0 (v_b == 0, or every row when s == 0): g = in, the very bits (no 0 / 0; -0.0 survives)
+ *   shift    raae_spec_augment's, on g: delta_b and the three-rounding interpolation as specified above, unchanged;
+ *            max_shift == 0 gives g[l] itself
+ *   noise    raae_spec_augment's: z = element (noise_goff + b L + l) of the step's Gaussian numbering, added by the
+ *            head's expression; spec_noise == 0 adds nothing
+ * With max_sigma == 0 the output is bit for bit raae_spec_augment's for the same max_shift, spec_noise and state, and
+ * with max_shift == 0 as well raae_step_begin's spec_out.  sigma_b and delta_b depend on the seed, the counter and b alone.
+ * One workgroup of 256 threads works on one row at a time: the row with its R-sample replicated halo, the 2 R + 1
+ * weights and g live in LDS, a barrier between the stages; min(B, 1024) workgroups, grid-stride over rows above that;
+ * dynamic LDS is sized for R = 64 whatever the plane's R is (4 * (2 L + 260) bytes).  No atomics and a fixed summation
+ * order: the result does not depend on the grid and a graph replay is bitwise the eager call.  spec and spec_out must
+ * not overlap.
+ *   B >= 1, 2 <= L <= 8192, no NULL pointer, max_shift finite and >= 0, max_sigma finite, >= 0 and ceil(3 s) <= 64 (all as
+ *   floats, compared BEFORE any conversion to an integer: 1e10 or 3e38 is refused), spec_noise not NaN, noise_goff >= 0 and a multiple of 4.  Anything else: RAAE_EINVAL, nothing is launched
+ *   and nothing written.
+ * Has the batched form: plane z reads its own argument block, so the trials of a batch may differ in max_sigma and
+ * max_shift. */
+int raae_spec_augment2(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
+                       int B, int L, double max_sigma, double max_shift, double spec_noise, long noise_goff,
+                       float* spec_out, void* stream);
 
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step and raae_spec_augment) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -696,7 +732,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 28
+#define RAAE_ABI_VERSION 29
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

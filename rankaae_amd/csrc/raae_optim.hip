@@ -730,6 +730,115 @@ __global__ __launch_bounds__(256) void spec_augment_kernel_m(const SpecAugArgs* 
     spec_augment_body(a);
 }
 
+// ---- resolution augmentation (config key `spec_broaden`): row b convolved with a Gaussian of its own width, then the
+// shift, then the noise ----
+// Behind the step head on the same state, like the kernel above.  Row b draws sigma_b = v_b * s, v_b = (g_b >> 8) *
+// 2^-24 with g_b = lowbias32(lowbias32(b + SPEC_BROADEN_OFF + k1) ^ k2): a third range of hash indices (dropout
+// elements are below 2^31, shift draws at 0x80000000 + b, b < 2^30).  A convolution reads its neighbours, so this is
+// the one augmentation kernel that stages: ONE workgroup works on ONE row at a time, in three stages with a barrier
+// between them --
+//   1. the row with R = ceil(3 s) replicated samples at either end -> LDS (`in`, L + 2 R floats), and the 2 R + 1
+//      weights w_j = expf(-(float)(j j) * q), q = 1 / (2 sigma sigma), w_0 = 1 -> LDS (one thread each);
+//   2. thread t, for l = t, t + 256, ...: g[l] = (sum_j w_j in[l + j]) / (sum_j w_j) -> LDS, both sums in ascending j,
+//      the first as ONE fmaf per tap (acc = fmaf(w_j, in, acc): one rounding per tap, and a product that cannot be
+//      contracted differently in another body -- there is one body), the second a plain fp32 sum every thread repeats
+//      beside it (the weight is in a register anyway; no reduction, no second barrier).  Lanes read consecutive LDS
+//      words and one broadcast word per tap: conflict free;
+//   3. out[b][l] = spec_shift_sample(g, l, delta_b) + noise: the functions of the kernel above, unchanged, on the LDS
+//      row.  A thread takes one QUAD of the step's Gaussian numbering (one Philox block) and the up to four samples of
+//      the row inside it, whatever L and the row's offset are: one body, no alignment case.
+// sigma_b == 0 (v_b == 0, or s == 0): stage 1 copies the row to g as it is and stage 2 is skipped -- the bits survive,
+// no 0 / 0.  expf, not __expf: the weights are specified to expf's accuracy.  q, the weights and sigma_b are computed
+// with contraction off; R is one value per plane (from its own argument block), the LDS image is laid out for R = 64
+// whatever R is, so that the planes of a batch share one launch geometry.  No atomics, fixed summation order: the
+// result does not depend on the grid, and a replay is bitwise the eager call.
+constexpr uint32_t SPEC_BROADEN_OFF = 0xC0000000u;
+constexpr int SPEC_BROADEN_RMAX = 64;
+constexpr int SPEC_BROADEN_LMAX = 8192;
+struct SpecAug2Args {
+    const float* spec; const long* idx; const int* cursor; const unsigned long long* rng_state; int B; int L;
+    float max_sigma; float max_shift; float spec_noise; long noise_goff; float* spec_out;
+};
+__host__ __device__ __forceinline__ float spec_broaden_radius_f(float s) {
+#pragma clang fp contract(off)
+    return ceilf(3.f * s);                                        // (one fp32 product, then the ceiling)
+}
+// the range check, in floating point BEFORE any conversion: 3 s may be beyond every int, or Inf for a finite s (false
+// for a NaN, too)
+__host__ __forceinline__ bool spec_broaden_radius_ok(float s) { return s >= 0.f && spec_broaden_radius_f(s) <= (float)SPEC_BROADEN_RMAX; }
+// (the entry point has checked the range: the conversion is exact)
+__device__ __forceinline__ int spec_broaden_radius(float s) { return (int)spec_broaden_radius_f(s); }
+__device__ __forceinline__ float spec_broaden_sigma(uint32_t b, uint32_t k1, uint32_t k2, float s) {
+#pragma clang fp contract(off)
+    const uint32_t g = raae::lowbias32(raae::lowbias32(b + SPEC_BROADEN_OFF + k1) ^ k2);
+    const float v = (float)(g >> 8) * (1.0f / 16777216.0f);       // exact: 24 bits
+    return v * s;                                                 // the only rounding
+}
+__device__ __forceinline__ float spec_broaden_q(float sigma) {
+#pragma clang fp contract(off)
+    const float s2 = sigma * sigma;                               // rounds
+    return 1.0f / (2.f * s2);                                     // 2 s2 is exact; the (correctly rounded) division rounds
+}
+__device__ __forceinline__ float spec_broaden_weight(int j, float q) {
+#pragma clang fp contract(off)
+    const float t = (float)(j * j) * q;                           // j j <= 4096 is exact; the product rounds
+    return j == 0 ? 1.f : expf(-t);
+}
+__device__ __forceinline__ void spec_augment2_body(const SpecAug2Args& a) {
+    extern __shared__ float s_aug2[];
+    const int L = a.L, R = spec_broaden_radius(a.max_sigma), tid = threadIdx.x;
+    float* s_in = s_aug2;                                         // L + 2 R of the L + 2 RMAX
+    float* s_w = s_aug2 + L + 2 * SPEC_BROADEN_RMAX;              // 2 R + 1 of the 2 RMAX + 4
+    float* s_g = s_w + 2 * SPEC_BROADEN_RMAX + 4;                 // L
+    const unsigned long long ctr = a.rng_state[0], seed = a.rng_state[1];
+    const uint32_t k1 = reinterpret_cast<const unsigned*>(a.rng_state + 2)[0];
+    const uint32_t k2 = reinterpret_cast<const unsigned*>(a.rng_state + 2)[1];
+    const long* idx = a.idx + (a.cursor[0] - a.B);
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const float* row = a.spec + (size_t)idx[b] * L;
+        const float sigma = spec_broaden_sigma((uint32_t)b, k1, k2, a.max_sigma);
+        if (sigma == 0.f) {                                       // (the whole workgroup agrees: one row, one sigma)
+            for (int l = tid; l < L; l += 256) s_g[l] = row[l];
+        } else {
+            for (int i = tid; i < L + 2 * R; i += 256) s_in[i] = row[min(max(i - R, 0), L - 1)];
+            if (tid <= 2 * R) s_w[tid] = spec_broaden_weight(tid - R, spec_broaden_q(sigma));
+            __syncthreads();
+            for (int l = tid; l < L; l += 256) {
+                float acc = 0.f, wsum = 0.f;
+                for (int j = 0; j <= 2 * R; ++j) {
+                    const float w = s_w[j];
+                    wsum += w;
+                    acc = fmaf(w, s_in[l + j], acc);
+                }
+                s_g[l] = acc / wsum;
+            }
+        }
+        __syncthreads();
+        const float delta = spec_shift_delta((uint32_t)b, k1, k2, a.max_shift);
+        const long e0 = a.noise_goff + (long)b * L;               // the row's first element in the Gaussian numbering
+        float* out = a.spec_out + (size_t)b * L;
+        for (long q4 = (e0 >> 2) + tid; q4 * 4 < e0 + L; q4 += 256) {
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            if (a.spec_noise != 0.f) normal4(q4, ctr, seed, z);
+            const long l0 = q4 * 4 - e0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const long l = l0 + k;
+                if (l < 0 || l >= L) continue;
+                float v = spec_shift_sample(s_g, (int)l, L, delta);
+                if (a.spec_noise != 0.f) v += z[k] * a.spec_noise;
+                out[l] = v;
+            }
+        }
+        __syncthreads();                                          // (the next row overwrites the LDS image)
+    }
+}
+__global__ __launch_bounds__(256) void spec_augment2_kernel(SpecAug2Args a) { spec_augment2_body(a); }
+__global__ __launch_bounds__(256) void spec_augment2_kernel_m(const SpecAug2Args* t) {
+    const SpecAug2Args a = t[blockIdx.z];
+    spec_augment2_body(a);
+}
+
 }  // namespace
 
 extern "C" int raae_adam_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
@@ -882,6 +991,33 @@ extern "C" int raae_spec_augment(const float* spec, const long* idx, const int* 
     long g = (((long)B * L + 3) / 4 + 255) / 256;
     if (g > 1024) g = 1024;
     raae::launch(spec_augment_kernel, spec_augment_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_spec_augment2(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
+                                  int B, int L, double max_sigma, double max_shift, double spec_noise, long noise_goff,
+                                  float* spec_out, void* stream) {
+    RAAE_CHECK_ARG(spec && idx && cursor && rng_state && spec_out && B >= 1 && L >= 2 && L <= SPEC_BROADEN_LMAX);
+    const float sg = (float)max_sigma, s = (float)max_shift, sn = (float)spec_noise;
+    RAAE_CHECK_ARG(max_shift >= 0.0 && s < INFINITY && sn == sn);      // (false for a NaN or Inf max_shift)
+    RAAE_CHECK_ARG(max_sigma >= 0.0 && sg < INFINITY);                 // (likewise)
+    RAAE_CHECK_ARG(spec_broaden_radius_ok(sg));                        // (a float comparison: 1e10 or 3e38 is refused here)
+    RAAE_CHECK_ARG((noise_goff & 3) == 0 && noise_goff >= 0);
+    const SpecAug2Args a = {spec, idx, cursor, rng_state, B, L, sg, s, sn, noise_goff, spec_out};
+    // one workgroup per row, at most 1024, above which the kernel grid-strides over rows; the LDS image is sized for
+    // the largest radius whatever this plane's is (one geometry per shape: the trials of a batch agree)
+    const size_t lds = sizeof(float) * (size_t)(2 * L + 4 * SPEC_BROADEN_RMAX + 4);
+    // the image of the longest row is 65.0 KiB: the runtime wants to be told about more than 64 KiB, once per kernel
+    // (the first call does it, for the largest L, whatever its own L is: no runtime call per launch or inside a capture
+    // after that)
+    static const hipError_t lds_limit = [] {
+        const int most = (int)(sizeof(float) * (2 * SPEC_BROADEN_LMAX + 4 * SPEC_BROADEN_RMAX + 4));
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(spec_augment2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(spec_augment2_kernel_m), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        return e;
+    }();
+    if (lds_limit != hipSuccess) return (int)lds_limit;
+    raae::launch(spec_augment2_kernel, spec_augment2_kernel_m, dim3(B < 1024 ? B : 1024), dim3(256), lds, (hipStream_t)stream, a);
     RAAE_LAUNCH_RET();
 }
 

@@ -26,7 +26,7 @@ from torch import nn
 from . import _lib, ops, schedule
 from .metrics import StyleMetrics
 from .schedule import Pass
-from .parameter import check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, spec_shift_of
+from .parameter import check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, spec_broaden_of, spec_shift_of
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -473,6 +473,9 @@ class StepEngine:
         # build-only key `spec_shift` (default absent: off), checked likewise: every training step resamples the rows of
         # its batch at a random per-row energy shift, one launch behind the step head (`emit_step`)
         self.spec_shift = spec_shift_of(cfg, rng_mode)
+        # build-only key `spec_broaden` (default absent: off), checked likewise: every training step convolves the rows
+        # of its batch with a Gaussian of a random per-row width, in front of the shift, in that one launch (`emit_step`)
+        self.spec_broaden = spec_broaden_of(cfg, rng_mode)
         if not torch.cuda.is_available():
             raise RuntimeError("rankaae_amd.engine needs an MI355X (no CPU/PyTorch fallback for the training path)")
         _lib.load()
@@ -876,6 +879,9 @@ class StepEngine:
         if self.spec_shift is not None:
             # the shift of row b is drawn at hash index SPEC_SHIFT_OFF + b: beyond every dropout element of the step
             assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF
+        if self.spec_broaden is not None:
+            # the width of row b is drawn at SPEC_BROADEN_OFF + b: beyond every dropout element and every shift draw
+            assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF and b < 2 ** 30
         P.rank_work = torch.empty(self._rank_work_bytes(b, rows_form=self.rank_pairs_global), dtype=torch.uint8, device=dev)
         if self.rank_pairs_global:
             P.aux_all = torch.empty(self.world_size * b, self.n_aux, device=dev)
@@ -1098,7 +1104,15 @@ class StepEngine:
         if P.stride is None:
             P.stride = stride
         assert P.stride == stride, "cursor stride is baked into the captured graph of this batch size"
-        if self.spec_shift is not None:
+        if self.spec_broaden is not None:
+            # `spec_broaden` (with or without `spec_shift`): the head as below, and ONE launch behind it that broadens
+            # the rows, shifts them (by nothing without `spec_shift`) and adds the noise
+            ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,
+                           self.train_spec, self.train_aux, self.perm, b, self.L, self.n_aux, 0.0, None, -P.noise - 1,
+                           P.spec, P.aux, tape)
+            ops.spec_augment2(self.train_spec, self.perm, self.cursor, self.rng_state, b, self.L, self.spec_broaden,
+                              self.spec_shift or 0.0, float(c["spec_noise"]), -P.noise - 1, P.spec)
+        elif self.spec_shift is not None:
             # `spec_shift`: the head ticks, fills the tape, gathers `aux` and writes the rows as they are (no noise);
             # the launch behind it overwrites `P.spec` with the rows resampled at their shifts, plus the noise -- every
             # phase of the step reads that one augmented batch

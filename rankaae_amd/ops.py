@@ -423,6 +423,20 @@ def spec_augment(spec, idx, cursor, rng_state, B, L, max_shift, spec_noise, nois
                                         _ptr(spec_out), _stream()), "raae_spec_augment")
 
 
+SPEC_BROADEN_OFF = 0xC0000000   # hash index of row 0's width draw: beyond every shift draw (SPEC_SHIFT_OFF + b, b < 2^30)
+
+
+def spec_augment2(spec, idx, cursor, rng_state, B, L, max_sigma, max_shift, spec_noise, noise_goff, spec_out):
+    """``raae_spec_augment2`` (config key ``spec_broaden``): ``spec_augment`` with row b convolved, in front of its shift,
+    with a normalised Gaussian of its own width ``sigma_b``, uniform in ``[0, max_sigma)`` grid points, from the step's
+    hash keys (replicated edges, radius ``ceil(3 max_sigma) <= 64``).  One launch, one workgroup per row, the row in
+    LDS; ``max_sigma = 0`` is ``spec_augment`` bit for bit."""
+    assert rng_state.dtype == torch.int64 and rng_state.numel() >= 3 and cursor.dtype == torch.int32
+    check(_lib.load().raae_spec_augment2(_ptr(spec), _ptr(idx, torch.int64), _ptr(cursor, torch.int32), _ptr(rng_state, torch.int64),
+                                         int(B), int(L), float(max_sigma), float(max_shift), float(spec_noise),
+                                         int(noise_goff), _ptr(spec_out), _stream()), "raae_spec_augment2")
+
+
 def slab_reduce(g_slabs, slab_stride, seg_nslab, n, out, max_nslab=512):
     check(_lib.load().raae_slab_reduce(_ptr(g_slabs), slab_stride, _ptr(seg_nslab, torch.int16), n, _ptr(out),
                                        int(max_nslab), _stream()), "raae_slab_reduce")

@@ -1,6 +1,9 @@
 """Immutable attribute namespace over the YAML configuration -- same surface as the
 reference's ``sc/utils/parameter.py:42-94`` (``Parameters``, ``from_yaml``, ``get``,
 ``update``, ``to_dict``; attribute assignment raises ``TypeError``)."""
+import ctypes
+import math
+
 import yaml
 
 from .model import AE_CLS_DICT  # noqa: F401  (re-exported like the reference does)
@@ -69,6 +72,41 @@ def spec_shift_of(cfg, rng_mode=None):
             not cfg.get("fused_step_begin", True):
         # (the parity mode exists for comparisons with the reference, which has no such draw to be in parity with)
         raise ValueError("spec_shift: device RNG with the fused step head only")
+    return float(value)
+
+
+SPEC_BROADEN_RMAX = 64      # the largest radius raae_spec_augment2 has LDS for
+
+
+def _spec_broaden_product(s):
+    """``3 s`` as the kernel computes it: ``s`` rounded to fp32, then the fp32 product (Inf for a large finite ``s``)."""
+    f = ctypes.c_float(float(s)).value
+    return ctypes.c_float(3.0 * f).value                     # (3 f is exact in double: rounded once, as on the device)
+
+
+def spec_broaden_radius(s):
+    """``ceil(3 s)`` as the kernel computes it, for an ``s`` whose product is finite; the range check itself compares
+    the product (``ceil(p) <= 64`` is ``p <= 64``), as the entry point does, before any conversion to an integer."""
+    return math.ceil(_spec_broaden_product(s))
+
+
+def spec_broaden_of(cfg, rng_mode=None):
+    """Build-only key ``spec_broaden`` (default absent / ``null``: off): a finite float ``s > 0`` with
+    ``ceil(3 s) <= 64``, the largest Gaussian sigma in grid points (it may be fractional).  Every training step then
+    convolves every row of its batch with a normalised Gaussian of its own width, uniform in ``[0, s)`` and drawn per
+    row on the device (replicated edges), before the energy shift (``spec_shift``) and the spectral noise; validation
+    and every export see the rows as they are.  Needs ``rng_mode: philox`` and ``fused_step_begin``, like
+    ``spec_shift``.  Returns the float, or None."""
+    value = cfg.get("spec_broaden", None)
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < float("inf")) or \
+            not _spec_broaden_product(value) <= SPEC_BROADEN_RMAX:
+        raise ValueError("spec_broaden must be absent, null or a finite number s with 0 < s and ceil(3 s) <= "
+                         f"{SPEC_BROADEN_RMAX} (the largest Gaussian sigma in grid points), not {value!r}")
+    if (rng_mode if rng_mode is not None else cfg.get("rng_mode", "philox")) != "philox" or \
+            not cfg.get("fused_step_begin", True):
+        raise ValueError("spec_broaden: device RNG with the fused step head only")
     return float(value)
 
 

@@ -112,6 +112,9 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     # draws themselves need nothing: they come from the engine's random state, which travels)
     if cfg.get("spec_shift") is not None:
         fp["cfg.spec_shift"] = float(cfg["spec_shift"])
+    # `spec_broaden` likewise
+    if cfg.get("spec_broaden") is not None:
+        fp["cfg.spec_broaden"] = float(cfg["spec_broaden"])
     spec = np.asarray(train_spec, dtype=np.float64)
     fp.update({"tile_rows_mult": int(tile_mult), "arena.n": int(arena_n), "rows.train": int(n_train),
                "rows.val": int(n_val), "spectra.sum": float(spec.sum()), "spectra.sum_sq": float((spec * spec).sum())})

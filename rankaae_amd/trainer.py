@@ -17,6 +17,9 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
                 epoch it is validated once (one ``EMA weights:`` log line) and written as ``final_ema.pt``
   ``spec_shift`` a number > 0 (default absent: off): every training step resamples each row of its batch at a random energy
                 shift of up to that many grid points, on the device, before the spectral noise; validation never shifts
+  ``spec_broaden`` a number s > 0 with ceil(3 s) <= 64 (default absent: off): every training step convolves each row of its
+                batch with a Gaussian of a random width of up to s grid points, on the device, before the shift and the
+                spectral noise; validation never broadens
 
 Data parallel (the north star's replacement of the ipyparallel trial farm): started under
 ``torch.distributed.run`` (WORLD_SIZE > 1) every rank builds the same ``Trainer``; rank r steps rows
@@ -38,7 +41,7 @@ from .dataloader import get_dataloaders
 from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
 from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, ema_decay_of,
-                        grad_clip_norm_of, resume_on, spec_shift_of)
+                        grad_clip_norm_of, resume_on, spec_broaden_of, spec_shift_of)
 from . import resume as resume_file
 
 
@@ -131,6 +134,7 @@ class Trainer:
         self.grad_clip_norm = grad_clip_norm_of(cfg)
         self.ema_decay = ema_decay_of(cfg)
         self.spec_shift = spec_shift_of(cfg)
+        self.spec_broaden = spec_broaden_of(cfg)
         self.detect_anomaly = detect_anomaly_on(cfg)
         # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
         # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
@@ -328,6 +332,8 @@ class Trainer:
             os.makedirs(chkpt_dir, exist_ok=True)
         if lead and self.spec_shift is not None:
             self.logger.info(f"spec_shift: rows shifted by up to ±{self.spec_shift:g} grid points")
+        if lead and self.spec_broaden is not None:
+            self.logger.info(f"spec_broaden: rows broadened by a Gaussian of up to σ = {self.spec_broaden:g} grid points")
         best_chpt_file, metrics = None, None
         if lead and self.resume:
             # rows are written every 10 epochs and the run went on after its last resume file: back to that epoch
