@@ -212,6 +212,25 @@ def _run(cfg, seed, spec, aux, steps, use_graph=True):
     return out
 
 
+def _slab_sum(G, seg, wide):
+    """The fp32 sum of the slabs ``G`` [S][n] (``seg``: slabs per element) in the order the update kernel of the
+    range's slab hint sums them: one after the other up to 16 slabs, the 8-chunk tree above (``wide``)."""
+    zero = torch.zeros_like(G[0])
+    top = int(seg.max())
+    if not wide:
+        g = zero.clone()
+        for r in range(top):
+            g = g + torch.where(seg > r, G[r], zero)
+        return g
+    ch = []
+    for c in range(8):                                  # chunk c: slabs c, c + 8, ... in order
+        g = zero.clone()
+        for r in range(c, top, 8):
+            g = g + torch.where(seg > r, G[r], zero)
+        ch.append(g)
+    return ((ch[0] + ch[1]) + (ch[2] + ch[3])) + ((ch[4] + ch[5]) + (ch[6] + ch[7]))     # the xor-shuffle tree
+
+
 @pytest.mark.parametrize("case", ["fc_small", "compact_small"])
 def test_teacher_forced_steps_match_the_clipped_reference(case):
     """Three steps of the smallest FC and compact configurations with every optimizer clipping on every step.  Per
@@ -234,22 +253,6 @@ def test_teacher_forced_steps_match_the_clipped_reference(case):
     # adversarial 6.23e-6, mutual_info 1.56e-6 (smoothness and all of fc_small, whose ranges sum in slab order anyway,
     # inside it).  The
     # figure is printed on every run ("captured gradient summed in slab order").
-
-    def _slab_sum(G, seg, wide):
-        zero = torch.zeros_like(G[0])
-        top = int(seg.max())
-        if not wide:
-            g = zero.clone()
-            for r in range(top):
-                g = g + torch.where(seg > r, G[r], zero)
-            return g
-        ch = []
-        for c in range(8):                                  # chunk c: slabs c, c + 8, ... in order
-            g = zero.clone()
-            for r in range(c, top, 8):
-                g = g + torch.where(seg > r, G[r], zero)
-            ch.append(g)
-        return ((ch[0] + ch[1]) + (ch[2] + ch[3])) + ((ch[4] + ch[5]) + (ch[6] + ch[7]))     # the xor-shuffle tree
 
     def pre(name, P):
         o = eng.opts[name]
