@@ -354,10 +354,12 @@ def smooth_lds_bytes(L):
     return 8 * L * 4 + SMOOTH_STATIC_LDS
 
 
-def disc_instance(n_real, n_fake):
-    """``(instance, nslab)``: the matrix-core form from 2048 rows; one slab per workgroup, 256 at most."""
+def disc_instance(n_real, n_fake, force=None):
+    """``(instance, nslab)``: the matrix-core form from 2048 rows; one slab per workgroup, 256 at most.  ``force``: the
+    value of the ``RAAE_DISC_MFMA`` tuning override (read once when the library loads): 0 / non-zero forces a form."""
     n = n_real + n_fake
-    return ("mfma" if n >= DISC_MFMA_ROWS else "valu"), min((n + DISC_TILE - 1) // DISC_TILE, DISC_MAXWG)
+    mm = n >= DISC_MFMA_ROWS if force is None or force < 0 else force != 0
+    return ("mfma" if mm else "valu"), min((n + DISC_TILE - 1) // DISC_TILE, DISC_MAXWG)
 
 
 def style_fwd_grid(B, C):

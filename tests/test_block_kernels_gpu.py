@@ -30,7 +30,9 @@ ones the dispatch selects from 1024 rows (``kBigMask`` of csrc/raae_conv.hip): `
 generic in every family, ``dec1`` too in ``bwd_a`` and ``wgrad``.  For the other table shapes the 1027- and
 4099-row cases run the PLAIN instance, as the package does; their compiled ``BIG`` instances (``enc1``, ``enc2``,
 ``dec0`` everywhere, ``dec1`` in ``fwd_a`` / ``fwd_b`` / ``bwd_b``) are reachable only through the
-``RAAE_BIG_MASK_*`` tuning overrides, which are read once when the library loads, and no test executes them.
+``RAAE_BIG_MASK_*`` tuning overrides, which are read once when the library loads: ``test_tuning_overrides_gpu.py`` runs
+the runners of this module on them (and on the plain instances at 1027 rows, and under the other tuning overrides) in
+child processes that load the library with the overrides set.
 
 Tolerances are those ``test_conv_family_fwd_bwd`` applies to the same quantities of the per-layer kernels: forward
 tensors 2e-5 relative + 2e-5; data gradients 5e-4 + 5e-5; weight, bias and slope gradients 5e-4 +
@@ -461,8 +463,9 @@ def _twice(rep, what, launch, read):
     return n1
 
 
-def run_teacher_forced(name, rows, gy_bn=False, need_dx=True, masked=True, off=0, update=False, tile=0):
-    """Returns the row count each of the four row-writing launches reported."""
+def run_teacher_forced(name, rows, gy_bn=False, need_dx=True, masked=True, off=0, update=False, tile=0, slabs_out=None):
+    """Returns the row count each of the four row-writing launches reported; ``slabs_out`` (a dict) receives the slab
+    counts of the weight-gradient tasks under "wgrad", in task order."""
     r = Rig(name, rows, gy_bn=gy_bn, need_dx=need_dx, masked=masked, off=off)
     rep = Report("forced " + _case_id(name, rows, gy_bn=gy_bn, no_dx=not need_dx, nomask=not masked, off=off,
                                       update=update, tile=tile))
@@ -502,7 +505,9 @@ def run_teacher_forced(name, rows, gy_bn=False, need_dx=True, masked=True, off=0
     _check_bwd_a(r, rep, b, n)
     # wgrad: reads the materialised gradients and the views they multiply
     r.force("dT2", "dT1", "dE1", "dEx", *(("dE2",) if r.excit else ()))
-    _twice(rep, "wgrad", lambda: tuple(r.wgrad()), lambda: dict(slabs=r.slabs.clone()))
+    ns = _twice(rep, "wgrad", lambda: tuple(r.wgrad()), lambda: dict(slabs=r.slabs.clone()))
+    if slabs_out is not None:
+        slabs_out["wgrad"] = tuple(ns)
     _check_wgrad(r, rep, b)
     rep.done()
     return counts
@@ -582,23 +587,29 @@ def test_grid_cap_loops_over_groups():
         assert n == MAXP, (kernel, n)
 
 
+def run_first_block(name, rows):
+    run_teacher_forced(name, rows, need_dx=False)
+    run_chained(name, rows, need_dx=False)
+
+
+def run_running_statistics(name, rows):
+    run_teacher_forced(name, rows, update=True)
+
+
 @pytest.mark.parametrize("name,rows", [("enc1", 37), ("dec1", 1027), ("gen_d", 37), ("dec3", 256)])
 def test_first_block_of_a_network(name, rows):
     """``dR`` = NULL: nothing upstream wants the input gradient; neither ``dR`` nor ``pdR`` is written."""
-    run_teacher_forced(name, rows, need_dx=False)
-    run_chained(name, rows, need_dx=False)
+    run_first_block(name, rows)
 
 
 @pytest.mark.parametrize("name,rows", [("enc1", 37), ("dec1", 256), ("dec2", 1027), ("gen_c", 37)])
 def test_running_statistics_move_as_batchnorm1d(name, rows):
     """``update_running`` on: the buffers move as ``torch.nn.BatchNorm1d`` moves them (momentum 0.1, unbiased
     variance), once, by workgroup 0 only."""
-    run_teacher_forced(name, rows, update=True)
+    run_running_statistics(name, rows)
 
 
-@pytest.mark.parametrize("name,rows", [("enc1", 37), ("dec1", 37), ("dec3", 1027), ("gen_c", 1027), ("gen_d", 37)])
-def test_eval_mode_forward(name, rows):
-    """Eval mode: running statistics normalise, there is no mask, and the running buffers stay as they were."""
+def run_eval_forward(name, rows):
     r = Rig(name, rows, masked=False)
     rep = Report("eval " + _case_id(name, rows))
     f = br.forward(r.m, r.x, None, train=False)
@@ -618,6 +629,12 @@ def test_eval_mode_forward(name, rows):
     for k, v in r.md.state_dict().items():
         rep.check(torch.equal(v, before[k]), f"{k} changed in an eval-mode forward")
     rep.done()
+
+
+@pytest.mark.parametrize("name,rows", [("enc1", 37), ("dec1", 37), ("dec3", 1027), ("gen_c", 1027), ("gen_d", 37)])
+def test_eval_mode_forward(name, rows):
+    """Eval mode: running statistics normalise, there is no mask, and the running buffers stay as they were."""
+    run_eval_forward(name, rows)
 
 
 @pytest.mark.parametrize("name,rows", [("enc0", 1027), ("dec2", 1027), ("dec3", 1027), ("dec3", 37), ("gen_d", 1027),

@@ -18,7 +18,7 @@ the batched (``_m``) twins of the five fused block kernels, one launch at a time
   co-launch is held to float64 alone and the test prints whether the bits agree and the largest difference in units of
   the bound (``PLAINvBIG`` lines).  Nothing promises bit equality between a plain and a BIG instance.
 * TWO PLANES: every row, and every ``KERNEL_m<KIND, BIG>`` twin of the block kernels that the default dispatch can
-  select, as a two-plane program (``raae_multi_build`` of two recorded trials with other seeds, and for the update
+  select (the 18 twins behind the ``RAAE_BIG_MASK_*`` overrides: ``test_tuning_overrides_gpu.py``), as a two-plane program (``raae_multi_build`` of two recorded trials with other seeds, and for the update
   another hyper block and step count): each plane holds the bits of its own single (co-)launch.
 
 FORM -> CASE (``test_co_reference_cpu.py`` recomputes it and fails on a gap)
@@ -56,6 +56,10 @@ if torch.cuda.is_available():
 SENT, MAXP = blocks.SENT, blocks.MAXP
 WIDE, CAPPED = 200, 17                          # max_nslab of the step module's "lanes8" / "stride_lanes8" layouts: both wide
 WORST = collections.defaultdict(float)          # quantity class -> largest share of its bound over the session
+MASK_ENV = ("FWD_A", "FWD_B", "BWD_B", "BWD_A", "WGRAD")
+# kBigMask as the library was loaded: the default unless a child process of test_tuning_overrides_gpu.py, started with the
+# RAAE_BIG_MASK_* overrides in its environment, says otherwise before it calls the runners below
+MASK = [co.BIG_MASK]
 PLAIN_V_BIG = []                                # (case, bits agree, largest difference in units of the bound)
 SLOW = {}
 T_START = [None]
@@ -434,9 +438,18 @@ def _count(fn):
     return None, buf.value.decode(), out
 
 
+def _mask_is_the_environments():
+    if MASK[0] == co.BIG_MASK:
+        assert not [k for k in os.environ if k.startswith("RAAE_BIG_MASK_")], "RAAE_BIG_MASK_* overrides are set"
+    env = tuple(int(os.environ.get("RAAE_BIG_MASK_" + n, str(d)), 0) for n, d in zip(MASK_ENV, co.BIG_MASK))
+    assert env == tuple(MASK[0]), f"RAAE_BIG_MASK_* overrides {env}, the cases were built for {MASK[0]}"
+
+
 def _mirror_holds(c, X, Y):
-    """The case's sides are the mirror's, no tuning override moves the answers, and ``raae_co_instance`` agrees."""
-    assert not [k for k in os.environ if k.startswith("RAAE_BIG_MASK_")], "RAAE_BIG_MASK_* overrides are set"
+    """The case's sides are the mirror's, no tuning override moves the answers (in a child process of
+    test_tuning_overrides_gpu.py: the overrides are exactly the mask the case was built with), and ``raae_co_instance``
+    agrees."""
+    _mask_is_the_environments()
     assert (X.spec(), Y.spec()) == (c.x, c.y), (X.spec(), Y.spec(), c.x, c.y)
     if c.via == "co":
         assert bool(ops.co_pairable(X.kind, X.args(), Y.kind, Y.args())) == (c.want is not None), \
@@ -463,7 +476,7 @@ def _run_pair(c, check=True):
     if check:
         X.check(rep)
         Y.check(rep)
-    big = [co.single_is_big(s, r) for s, r in zip((c.x, c.y), c.rows)]
+    big = [co.single_is_big(s, r, MASK[0]) for s, r in zip((c.x, c.y), c.rows)]
     diff = [_differ(g, a) for g, a in zip(got, alone)]
     for i, what in enumerate("xy"):
         if c.want is None or not big[i]:
@@ -608,8 +621,8 @@ def test_pair_two_planes(c):
 @pytest.mark.parametrize("kind,name,rows", BLOCK_PLANE_CASES, ids=lambda v: str(v))
 def test_block_kernel_two_planes(kind, name, rows):
     """``KERNEL_m<KIND, BIG>`` of the five block kernels alone: the plain twins at 37 rows, at 1027 rows every twin the
-    default mask sends to BIG."""
-    assert not [k for k in os.environ if k.startswith("RAAE_BIG_MASK_")], "RAAE_BIG_MASK_* overrides are set"
+    default mask sends to BIG (the other BIG twins: ``test_tuning_overrides_gpu.py``)."""
+    _mask_is_the_environments()
     _two_planes(f"blk_{kind}_{name}@{rows}", lambda seed: (BlockSide(kind, name, rows, seed),), lambda s: s[0].single())
 
 

@@ -29,9 +29,9 @@ MSE and BCE losses, ``raae_loss_finalize``, ``raae_disc_input``, ``raae_scale_by
 
 FORM -> CASE (the table test of ``test_loss_reference_cpu.py`` recomputes this map and fails on a gap):
   rank pairs   KA 1..16, R = 1, unmasked / masked: ka{K}_u / ka{K}_m (B = 37); tile edges tile{B}_k3 / _k7
-               KA {1,3,7,11,16}, R = 4, column blocks, unmasked / masked: r4_{1025,1030}_k{K}_{u,m}; the empty last
-               column block: r4_1030_k1_*; the other KA at R = 4 share rank_pairs_body's R loop with these (the 64
-               instances are KA x R x masked; R = 4 is run at five KA per mask, named here)
+               KA 1..16, R = 4, column blocks, unmasked / masked: r4_1025_k{K}_{u,m}; KA {1,3,7,11,16} also at 1030
+               rows: r4_1030_k{K}_{u,m}; the empty last column block: r4_1030_k1_* (the 64 instances are KA x R x
+               masked: every one has a case of its own)
                R = 4, nj = 1: big_8192; nj = 2: big_8184; grid stride: big_16392_u / big_16392_m
                R = 1 with nj > 1 (rows form only): rows_1030_515_*; one-row and R = 4 shares rows_1030_1_1029_* /
                rows_1030_1029_1_*; small splits rows_40_*
@@ -80,7 +80,10 @@ RANK_CASES = ([RankCase(f"ka{K}_{'m' if m else 'u'}", 37, K, m, False) for K in 
               [RankCase(f"tile{B}_k{K}_{'m' if m else 'u'}", B, K, m, False)
                for B in (2, 255, 256, 257, 513) for K in (3, 7) for m in (False, True)] +
               [RankCase(f"r4_{B}_k{K}_{'m' if m else 'u'}", B, K, m, False)
-               for B in (1025, 1030) for K in (1, 3, 7, 11, 16) for m in (False, True)])
+               for B in (1025, 1030) for K in (1, 3, 7, 11, 16) for m in (False, True)] +
+              # the other eleven descriptor counts at R = 4 (any run above 1024 rows with 2, 4, 5, 6, ... descriptors)
+              [RankCase(f"r4_1025_k{K}_{'m' if m else 'u'}", 1025, K, m, False)
+               for K in (2, 4, 5, 6, 8, 9, 10, 12, 13, 14, 15) for m in (False, True)])
 BIG_RANK_CASES = [RankCase("big_8192", 8192, 16, False, True), RankCase("big_8184", 8184, 16, False, True),
                   RankCase("big_16392_u", 16392, 16, False, True), RankCase("big_16392_m", 16392, 16, True, True)]
 RANK_BY_NAME = {c.name: c for c in RANK_CASES + BIG_RANK_CASES}
@@ -853,15 +856,16 @@ class DiscDev:
                               self.dstyles.t, self.partial.t, self.ticket, self.loss.t)
 
 
-@pytest.mark.parametrize("name", [c.name for c in DISC_CASES])
-def test_disc_fused(name):
+def run_disc_fused(name, force=None):
+    """One case against float64.  ``force``: the value of ``RAAE_DISC_MFMA`` the library was loaded under (None: unset),
+    which the mirror follows; returns (instance, nslab)."""
     c = DISC_BY_NAME[name]
     rep = Report(name)
     t = disc_data(name)
     ref, near = t["ref"], t["near"]
     dv = DiscDev(c, t)
     nsl = _twice(rep, dv.bufs, dv.launch)
-    inst, want_n = lr.disc_instance(c.n_real, c.n_fake)
+    inst, want_n = lr.disc_instance(c.n_real, c.n_fake, force)
     rep.check(nsl == want_n, f"nslab {nsl}, the mirror of the {inst} instance gives {want_n}")
     rep.check(int(dv.ticket) == 0, f"the ticket reads {int(dv.ticket)}")
     rep.check(bool((dv.slabs.t[nsl:] == SENT).all()), "slab rows beyond nslab touched")
@@ -895,6 +899,12 @@ def test_disc_fused(name):
             rep.check(n_bad <= n_near * 130 and (n_bad == 0 or e.max() <= 0.05 * np.abs(w).max() + 1e-7),
                       f"d{k}: {n_bad} entries miss (max err {e.max():.3e}) with {n_near} near-zero rows")
     rep.done()
+    return inst, nsl
+
+
+@pytest.mark.parametrize("name", [c.name for c in DISC_CASES])
+def test_disc_fused(name):
+    run_disc_fused(name)
 
 
 # ==================================================================================================== batched planes

@@ -281,6 +281,8 @@ def test_mirror_of_the_dispatch():
     assert (lr.recon_nparts(1), lr.recon_nparts(2049), lr.mse_nparts(512 * 1024 + 3), lr.mse_nparts(1)) == (1, 512, 512, 1)
     assert lr.disc_instance(1000, 1047) == ("valu", 128) and lr.disc_instance(1000, 1048) == ("mfma", 128)
     assert lr.disc_instance(2056, 2057) == ("mfma", 256) and lr.disc_instance(1, 1) == ("valu", 1)
+    assert lr.disc_instance(1, 1, force=1) == ("mfma", 1) and lr.disc_instance(2056, 2057, force=0) == ("valu", 256)
+    assert lr.disc_instance(1000, 1048, force=-1) == ("mfma", 128)
     assert lr.smooth_instance(17) == "taps17" and lr.smooth_instance(33) == "generic"
     assert lr.smooth_lds_bytes(2048) > 65536 and lr.smooth_lds_bytes(4096) < 163840
 
@@ -300,8 +302,8 @@ def test_case_table_reaches_every_form():
     for K in range(1, 17):
         for m in (False, True):
             assert have[(K, 1, m)], f"rank_pairs_body<{K}, 1, {m}> has no case"
-    # R = 4: the KA the issue names, masked and not, each with column blocks
-    for K in (1, 3, 7, 11, 16):
+    # R = 4: all 16 KA, masked and not, each with column blocks
+    for K in range(1, 17):
         for m in (False, True):
             names = have[(K, 4, m)]
             assert any(forms[n]["multi_block"] for n in names), f"rank_pairs_body<{K}, 4, {m}> has no case with column blocks"
