@@ -212,6 +212,27 @@ int raae_rank_rows_masked_finish(const double* totals, int n_all, int nrows, int
  * out: k doubles W_c, then k(k-1)/2 doubles rho_(p,q), p < q, in itertools.combinations order. */
 int raae_style_metrics(const float* z, int n, int k, const double* a_coef, double* work, double* out, void* stream);
 
+/* Kendall's tau-b of style k against descriptor k on the rows labelled for k (ABI 30; config key `rank_metrics`): what
+ * scipy.stats.kendalltau(d_k, z_k, variant="b") returns there, from exact pair counts, where the validation styles
+ * already are.  d [n][ldd] descriptors (a cell that is not finite is a missing label and takes its row out of that
+ * descriptor's pairs), z [n][ldz] styles; column k of z meets column k of d, k < n_aux <= 16, ldd >= n_aux,
+ * ldz >= n_aux, n >= 1 (anything else: RAAE_EINVAL before a launch).
+ *   counts [n_aux][6] 64-bit integers over the unordered pairs of labelled rows: C concordant, D discordant, Tx tied in
+ *   the descriptor only, Ty tied in the style only, Txy tied in both, and m = the labelled rows.  A pair is classified
+ *   by the order (<, >, ==) of the stored values alone -- no difference, no product, no denormal mode: two subnormals
+ *   one ulp apart are ordered, +0 and -0 are tied.
+ *   tau [n_aux] doubles: (C - D) / sqrt(tot - (Tx + Txy)) / sqrt(tot - (Ty + Txy)), tot = m (m - 1) / 2, in scipy's
+ *   order of operations; NaN when m < 2 or a factor is zero (a constant column), as scipy 1.15.3 returns.  Styles that
+ *   are not finite give counts without meaning and read nothing out of bounds.
+ *   work: >= raae_kendall_tau_work_bytes(n, n_aux) bytes of per-workgroup partial counts; linear in n (48 bytes per
+ *   descriptor, 256-row tile and column split; 140 KB at n = 150 000, n_aux = 5).
+ * Two launches, no atomics, both with the batched (gridDim.z) form: a tiled pass over the unordered pairs -- 256-row
+ * tiles whose unordered tile pairs are dealt to the row tiles cyclically (a column tile may lie before its row tile;
+ * a diagonal tile counts only the rows behind each row), every pair met once -- and a finish. */
+long raae_kendall_tau_work_bytes(int n, int n_aux);
+int raae_kendall_tau(const float* d, int ldd, const float* z, int ldz, int n, int n_aux, void* work, long long* counts,
+                     double* tau, void* stream);
+
 /* out[g][l] = mean over s of x[g][s][l], x [groups][per][L]: the n_sampling average of the report's decoder
  * sweeps (sc/report/analysis.py:78-86, `decoder(con_c).reshape(n_spec, n_sampling, L).mean(axis=1)`). */
 int raae_group_mean(const float* x, int groups, int per, int L, float* out, void* stream);
@@ -687,7 +708,7 @@ int raae_spec_augment2(const float* spec, const long* idx, const int* cursor, co
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2, since ABI 30 raae_kendall_tau) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -732,7 +753,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 29
+#define RAAE_ABI_VERSION 30
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -2,7 +2,8 @@
 """``train_sc -c <config.yaml> [-w <work_dir>]`` -- same command line, per-trial directory layout
 and log files as the reference's ``sc/cmd/train_sc.py:105-157`` (``training/job_<k>/{messages.txt,
 losses.csv,final.pt}``, ``main_process_message.txt``; with the config key ``ema_decay`` also ``final_ema.pt``, the moving
-average of the weights, and one ``EMA weights:`` line in ``messages.txt``), with the training itself on the MI355X HIP
+average of the weights, and one ``EMA weights:`` line in ``messages.txt``; with ``rank_metrics: true`` also
+``rank_metrics.csv``, one row of Kendall tau-b values per epoch), with the training itself on the MI355X HIP
 engine.  The ipyparallel engine farm (``train_sc.py:19-45``) becomes one worker process per visible GPU:
 trial ``k`` runs on worker ``k mod n`` and worker ``w`` uses GPU ``w mod ngpus`` (``RANKAAE_TRIAL_WORKERS``
 overrides ``n``).  Several trials share a GPU (config key ``trials_per_gpu``, default 4 when ``trials > 1``): a 256-row

@@ -159,7 +159,164 @@ __global__ __launch_bounds__(256) void group_mean_kernel(const float* __restrict
     }
 }
 
+// ---- Kendall's tau-b of style k against descriptor k (ABI 30; config key `rank_metrics`) --------------------------------
+// What scipy.stats.kendalltau(d_k, z_k, variant="b") returns on the rows labelled for descriptor k, from exact pair
+// counts.  kendall_pairs_kernel: grid (T * S, n_aux), T = ceil(n / 256) row tiles.  A thread owns one row of its row
+// tile and meets the rows of a column tile staged in LDS (every lane reads the same address: a broadcast).  The
+// unordered tile pairs are dealt out cyclically: row tile ti takes the column tiles (ti + o) mod T, o = 0 .. T / 2 (for
+// an even T the offset T / 2 belongs to the lower half of the row tiles alone), so every tile pair is met once, every
+// row tile does the same work, and the partials grow with T, not T^2; split s of S takes the offsets s, s + S, ...
+// The diagonal tile (o = 0) counts j behind i only.  Rows without a label (a descriptor cell that is not finite) never
+// reach the LDS tile: the stage compacts the labelled rows in row order, which also keeps "behind" meaningful there.
+//
+// A pair is classified by <, >, == of the stored values, taken on their order-preserving integer keys (the bits, with
+// the magnitude of a negative value inverted, and -0 as +0): the same order and the same ties as the float comparisons
+// for every value that is not NaN, with no arithmetic on the values and no dependence on the denormal mode -- two
+// subnormals one ulp apart are ordered.  A NaN style is just some key: counts without meaning, nothing out of bounds.
+constexpr int kKtTile = 256;
+constexpr int kKtMaxSplit = 8;
+struct KendallPart { long long c[6]; };     // C, D, Tx, Ty, Txy of the workgroup's pairs; labelled rows of its row tile
+
+__device__ __forceinline__ int kendall_key(float x) {
+    int b = __float_as_int(x);
+    b = b < 0 ? b ^ 0x7fffffff : b;
+    return b == -1 ? 0 : b;                 // -0.0 (0x80000000 -> -1) ties with +0.0
+}
+__device__ __forceinline__ bool kendall_labelled(float d) { return (__float_as_uint(d) & 0x7f800000u) != 0x7f800000u; }
+
+__device__ __forceinline__ long long kendall_block_sum(long long v, long long* sh) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+struct KendallPairsArgs { const float* d; int ldd; const float* z; int ldz; int n; int T; int S; KendallPart* part; };
+__device__ __forceinline__ void kendall_pairs_body(const float* __restrict__ d, int ldd, const float* __restrict__ z,
+                                                   int ldz, int n, int T, int S, KendallPart* __restrict__ part) {
+    __shared__ int2 tile[kKtTile];          // {descriptor key, style key} of the column tile's labelled rows
+    __shared__ int wave_n[4];
+    __shared__ long long red[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ti = blockIdx.x / S, s = blockIdx.x - ti * S, k = blockIdx.y;
+    const int i = ti * kKtTile + tid;
+    int di = 0, zi = 0;
+    bool vi = false;
+    if (i < n) {
+        const float dv = d[(size_t)i * ldd + k];
+        vi = kendall_labelled(dv);
+        di = kendall_key(dv); zi = kendall_key(z[(size_t)i * ldz + k]);
+    }
+    const int H = T / 2;
+    const int omax = ((T & 1) || ti < H) ? H : H - 1;
+    int nc = 0, nd = 0, ntx = 0, nty = 0, ntxy = 0;
+    for (int o = s; o <= omax; o += S) {
+        const int tj = ti + o < T ? ti + o : ti + o - T;
+        const int j = tj * kKtTile + tid;
+        int dj = 0, zj = 0;
+        bool vj = false;
+        if (j < n) {
+            const float dv = d[(size_t)j * ldd + k];
+            vj = kendall_labelled(dv);
+            dj = kendall_key(dv); zj = kendall_key(z[(size_t)j * ldz + k]);
+        }
+        const unsigned long long live = __ballot(vj);
+        if (lane == 0) wave_n[wave] = __popcll(live);
+        __syncthreads();                    // the counts are there, and every wave has left the previous tile
+        int pos = __popcll(live & ((1ull << lane) - 1ull)), nv = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int c = wave_n[w]; pos += w < wave ? c : 0; nv += c; }
+        if (vj) tile[pos] = make_int2(dj, zj);
+        __syncthreads();
+        // diagonal tile: row i is the tile's row `pos` (tj == ti, so vj == vi), and pairs with the rows behind it
+        const int first = vi ? (o == 0 ? pos + 1 : 0) : nv;
+#pragma unroll 4
+        for (int jj = first; jj < nv; ++jj) {
+            const int2 t = tile[jj];
+            const bool dl = t.x < di, dg = t.x > di, zl = t.y < zi, zg = t.y > zi;
+            const bool de = !(dl | dg), ze = !(zl | zg);
+            nc += (dl & zl) | (dg & zg);
+            nd += (dl & zg) | (dg & zl);
+            ntx += de & !ze;
+            nty += ze & !de;
+            ntxy += de & ze;
+        }
+    }
+    const long long lab = (s == 0 && vi) ? 1 : 0;
+    const long long t0 = kendall_block_sum(nc, red), t1 = kendall_block_sum(nd, red), t2 = kendall_block_sum(ntx, red);
+    const long long t3 = kendall_block_sum(nty, red), t4 = kendall_block_sum(ntxy, red), t5 = kendall_block_sum(lab, red);
+    if (tid == 0) {
+        KendallPart p;
+        p.c[0] = t0; p.c[1] = t1; p.c[2] = t2; p.c[3] = t3; p.c[4] = t4; p.c[5] = t5;
+        part[(size_t)k * gridDim.x + blockIdx.x] = p;
+    }
+}
+__global__ __launch_bounds__(256) void kendall_pairs_kernel(KendallPairsArgs a) {
+    kendall_pairs_body(a.d, a.ldd, a.z, a.ldz, a.n, a.T, a.S, a.part);
+}
+__global__ __launch_bounds__(256) void kendall_pairs_kernel_m(const KendallPairsArgs* t) {
+    const KendallPairsArgs a = t[blockIdx.z];
+    kendall_pairs_body(a.d, a.ldd, a.z, a.ldz, a.n, a.T, a.S, a.part);
+}
+
+// grid (n_aux): workgroup k adds descriptor k's partials (integers: any order gives the same sums; this one is fixed)
+// and forms tau in double in scipy's order of operations.
+struct KendallFinArgs { const KendallPart* part; int nparts; long long* counts; double* tau; };
+__device__ __forceinline__ void kendall_finish_body(const KendallPart* __restrict__ part, int nparts,
+                                                    long long* __restrict__ counts, double* __restrict__ tau) {
+    __shared__ long long red[4];
+    const int tid = threadIdx.x, k = blockIdx.x;
+    const KendallPart* p = part + (size_t)k * nparts;
+    long long a0 = 0, a1 = 0, a2 = 0, a3 = 0, a4 = 0, a5 = 0;
+    for (int w = tid; w < nparts; w += 256) {
+        const KendallPart v = p[w];
+        a0 += v.c[0]; a1 += v.c[1]; a2 += v.c[2]; a3 += v.c[3]; a4 += v.c[4]; a5 += v.c[5];
+    }
+    const long long C_ = kendall_block_sum(a0, red), D_ = kendall_block_sum(a1, red), Tx = kendall_block_sum(a2, red);
+    const long long Ty = kendall_block_sum(a3, red), Txy = kendall_block_sum(a4, red), m = kendall_block_sum(a5, red);
+    if (tid == 0) {
+        long long* c = counts + (size_t)k * 6;
+        c[0] = C_; c[1] = D_; c[2] = Tx; c[3] = Ty; c[4] = Txy; c[5] = m;
+        const long long tot = m * (m - 1) / 2, fx = tot - (Tx + Txy), fy = tot - (Ty + Txy);
+        double t = __longlong_as_double(0x7ff8000000000000LL);       // fewer than two rows, or a constant column
+        if (m >= 2 && fx != 0 && fy != 0) t = (double)(C_ - D_) / sqrt((double)fx) / sqrt((double)fy);
+        tau[k] = t;
+    }
+}
+__global__ __launch_bounds__(256) void kendall_finish_kernel(KendallFinArgs a) { kendall_finish_body(a.part, a.nparts, a.counts, a.tau); }
+__global__ __launch_bounds__(256) void kendall_finish_kernel_m(const KendallFinArgs* t) {
+    const KendallFinArgs a = t[blockIdx.z];
+    kendall_finish_body(a.part, a.nparts, a.counts, a.tau);
+}
+
+// column-tile splits per row tile: enough workgroups for the chip while there are few row tiles, one from ~200 row tiles
+// on (the partials stay linear in n: T * S <= min(kKtMaxSplit * T, 1024 / n_aux + T) per descriptor)
+static int kendall_split(int T, int n_aux) {
+    const int want = raae::cdiv(1024, (long)T * n_aux), most = T / 2 + 1;
+    const int s = want < most ? want : most;
+    return s < 1 ? 1 : (s > kKtMaxSplit ? kKtMaxSplit : s);
+}
+
 }  // namespace
+
+extern "C" long raae_kendall_tau_work_bytes(int n, int n_aux) {
+    if (n < 1 || n_aux < 1 || n_aux > 16) return 0;
+    const int T = raae::cdiv(n, kKtTile);
+    return (long)T * kendall_split(T, n_aux) * n_aux * (long)sizeof(KendallPart);
+}
+
+extern "C" int raae_kendall_tau(const float* d, int ldd, const float* z, int ldz, int n, int n_aux, void* work,
+                                long long* counts, double* tau, void* stream) {
+    RAAE_CHECK_ARG(d && z && work && counts && tau && n >= 1 && n_aux >= 1 && n_aux <= 16 && ldd >= n_aux && ldz >= n_aux);
+    const int T = raae::cdiv(n, kKtTile), S = kendall_split(T, n_aux);
+    const KendallPairsArgs pa = {d, ldd, z, ldz, n, T, S, (KendallPart*)work};
+    raae::launch(kendall_pairs_kernel, kendall_pairs_kernel_m, dim3(T * S, n_aux), dim3(256), 0, (hipStream_t)stream, pa);
+    const KendallFinArgs fa = {(const KendallPart*)work, T * S, counts, tau};
+    raae::launch(kendall_finish_kernel, kendall_finish_kernel_m, dim3(n_aux), dim3(256), 0, (hipStream_t)stream, fa);
+    RAAE_LAUNCH_RET();
+}
 
 extern "C" int raae_group_mean(const float* x, int groups, int per, int L, float* out, void* stream) {
     RAAE_CHECK_ARG(x && out && groups > 0 && per > 0 && L > 0);

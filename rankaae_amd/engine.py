@@ -24,9 +24,10 @@ import torch
 from torch import nn
 
 from . import _lib, ops, schedule
-from .metrics import StyleMetrics
+from .metrics import KendallTau, StyleMetrics
 from .schedule import Pass
-from .parameter import check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, spec_broaden_of, spec_shift_of
+from .parameter import (check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, rank_metrics_on,
+                        spec_broaden_of, spec_shift_of)
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -476,6 +477,9 @@ class StepEngine:
         # build-only key `spec_broaden` (default absent: off), checked likewise: every training step convolves the rows
         # of its batch with a Gaussian of a random per-row width, in front of the shift, in that one launch (`emit_step`)
         self.spec_broaden = spec_broaden_of(cfg, rng_mode)
+        # build-only key `rank_metrics` (default false), checked likewise: every validation also forms Kendall's tau-b of
+        # each descriptor against its style, two launches behind the style metrics (`validate`)
+        self.rank_metrics = rank_metrics_on(cfg)
         if not torch.cuda.is_available():
             raise RuntimeError("rankaae_amd.engine needs an MI355X (no CPU/PyTorch fallback for the training path)")
         _lib.load()
@@ -1619,6 +1623,7 @@ class StepEngine:
             V.ticket = torch.zeros(1, dtype=torch.int32, device=dev)
             V.out = torch.zeros(8, device=dev)
             V.metrics = StyleMetrics(nv, ns, dev)
+            V.kendall = KendallTau(nv, self.n_aux, dev) if self.rank_metrics else None
             self.plans[key] = V
         V = self.plans[key]
         self._val_plan = V
@@ -1662,6 +1667,10 @@ class StepEngine:
             ops.mse_fwd_bwd(z_rec, z_s, nv * ns, V.lpart, None, fin=(1.0, V.out, 3, -1, V.ticket))
             self.disc.forward_backward(V.disc, V.sl_disc, z, V.out[0:1], train=False)
             V.metrics.launch(z)      # Shapiro-Wilk W per style, Spearman rho per pair (trainer.py:286-292)
+            if V.kendall is not None:
+                # `rank_metrics`: tau-b of style k against descriptor k over the rows labelled for k.  Data parallel:
+                # every rank runs the whole pass on the same styles, replicated like the style metrics
+                V.kendall.launch(val_aux, z)
             return z
 
         if _phase == "emit":
@@ -1693,3 +1702,12 @@ class StepEngine:
         """``(W[nstyle], rho[pairs])`` of the styles of the last ``validate`` call (float64 numpy): what the
         reference's ``shapiro(x).statistic`` / ``spearmanr(a, b).correlation`` return for those columns."""
         return self._val_plan.metrics.read()
+
+    def val_rank_metrics(self):
+        """``(tau[n_aux] float64, counts[n_aux, 6] int64)`` of the last ``validate`` call (numpy; config key
+        ``rank_metrics``): Kendall's tau-b of style ``k`` against descriptor ``k`` over the validation rows labelled for
+        ``k`` -- ``scipy.stats.kendalltau(aux[:, k], z[:, k], variant="b")`` there -- and the pair counts C, D, Tx, Ty,
+        Txy with the number of those rows.  ``RuntimeError`` on an engine without the key."""
+        if not self.rank_metrics:
+            raise RuntimeError("val_rank_metrics(): this engine forms no rank metrics (config key rank_metrics)")
+        return self._val_plan.kendall.read()

@@ -79,3 +79,28 @@ class StyleMetrics:
     def read(self):
         v = self.out.cpu().numpy()
         return v[:self.k], v[self.k:]
+
+
+class KendallTau:
+    """Kendall's tau-b of style column ``k`` against descriptor column ``k`` on the device (``raae_kendall_tau``; config
+    key ``rank_metrics``).  Device buffers for one ``(n, n_aux)``; ``launch(d, z)`` enqueues the two kernels on the
+    current stream without a host synchronisation (it is capturable) -- ``d [n, ldd]`` descriptors, NaN cells being
+    missing labels, ``z [n, ldz]`` styles, ``ldd, ldz >= n_aux`` -- and ``read()`` returns ``(tau[n_aux] float64,
+    counts[n_aux, 6] int64)`` as numpy: per descriptor the concordant, discordant, descriptor-tied, style-tied and
+    doubly tied pairs among the labelled rows, and the number of those rows."""
+
+    def __init__(self, n, n_aux, device):
+        self.n, self.n_aux = int(n), int(n_aux)
+        if self.n < 1 or not 1 <= self.n_aux <= 16:
+            raise ValueError(f"KendallTau needs n >= 1 and 1 <= n_aux <= 16, not n = {n}, n_aux = {n_aux}")
+        self.work = torch.empty(ops.kendall_tau_work_bytes(self.n, self.n_aux), dtype=torch.uint8, device=device)
+        self.counts = torch.zeros(self.n_aux, 6, dtype=torch.int64, device=device)
+        self.tau = torch.zeros(self.n_aux, dtype=torch.float64, device=device)
+
+    def launch(self, d, z):
+        assert d.dim() == 2 and z.dim() == 2 and d.shape[0] == self.n and z.shape[0] == self.n, (d.shape, z.shape)
+        assert d.shape[1] >= self.n_aux and z.shape[1] >= self.n_aux, (d.shape, z.shape, self.n_aux)
+        ops.kendall_tau(d, d.shape[1], z, z.shape[1], self.n, self.n_aux, self.work, self.counts, self.tau)
+
+    def read(self):
+        return self.tau.cpu().numpy(), self.counts.cpu().numpy()

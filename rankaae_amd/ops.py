@@ -249,6 +249,20 @@ def style_metrics(z, n, k, a_coef, work, out):
                                          _ptr(out, torch.float64), _stream()), "raae_style_metrics")
 
 
+def kendall_tau_work_bytes(n, n_aux):
+    return int(_lib.load().raae_kendall_tau_work_bytes(n, n_aux))
+
+
+def kendall_tau(d, ldd, z, ldz, n, n_aux, work, counts, tau):
+    """Kendall's tau-b of style column k against descriptor column k (``raae_kendall_tau``): ``counts`` int64
+    ``[n_aux, 6]``, ``tau`` float64 ``[n_aux]``, ``work`` a byte buffer of ``kendall_tau_work_bytes``."""
+    assert d.numel() >= (n - 1) * ldd + n_aux and z.numel() >= (n - 1) * ldz + n_aux
+    assert counts.numel() >= 6 * n_aux and tau.numel() >= n_aux
+    assert work.numel() * work.element_size() >= kendall_tau_work_bytes(n, n_aux) > 0
+    check(_lib.load().raae_kendall_tau(_ptr(d), ldd, _ptr(z), ldz, n, n_aux, _ptr(work, None), _ptr(counts, torch.int64),
+                                       _ptr(tau, torch.float64), _stream()), "raae_kendall_tau")
+
+
 def group_mean(x, groups, per, L, out):
     check(_lib.load().raae_group_mean(_ptr(x), groups, per, L, _ptr(out), _stream()), "raae_group_mean")
 

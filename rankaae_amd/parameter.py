@@ -133,6 +133,17 @@ def detect_anomaly_on(cfg):
     return value
 
 
+def rank_metrics_on(cfg):
+    """Build-only key ``rank_metrics`` (default ``false``): ``true`` makes every validation also form, on the device,
+    Kendall's tau-b of each descriptor against its style over the validation rows labelled for it
+    (``raae_kendall_tau``), and ``Trainer`` append them to ``rank_metrics.csv`` every epoch.  A bool and nothing else:
+    ``"true"``, ``1`` and the like are a ``ValueError``."""
+    value = cfg.get("rank_metrics", False)
+    if not isinstance(value, bool):
+        raise ValueError(f"rank_metrics must be true or false, not {value!r}")
+    return value
+
+
 def checkpoint_every_of(cfg):
     """Build-only key ``checkpoint_every`` (default 0: off): an integer N >= 0; with N > 0 ``Trainer`` writes the
     trial's resume file (``rankaae_amd/resume.py``) after every N-th epoch, and when a stop request ends the run."""

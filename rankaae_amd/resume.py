@@ -115,6 +115,8 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     # `spec_broaden` likewise
     if cfg.get("spec_broaden") is not None:
         fp["cfg.spec_broaden"] = float(cfg["spec_broaden"])
+    # (`rank_metrics` stays out: it adds a file beside the run and shapes nothing of the training, so a run may be
+    # resumed with the key turned on or off)
     spec = np.asarray(train_spec, dtype=np.float64)
     fp.update({"tile_rows_mult": int(tile_mult), "arena.n": int(arena_n), "rows.train": int(n_train),
                "rows.val": int(n_val), "spectra.sum": float(spec.sum()), "spectra.sum_sq": float((spec * spec).sum())})
@@ -132,7 +134,8 @@ def check_fingerprint(saved, now, path="resume.pt"):
 def truncate_losses_csv(path, last_epoch):
     """Cut ``losses.csv`` down to its header and the rows with ``epoch <= last_epoch`` (rows are written every 10
     epochs, and the run went on after its last resume file); ``last_epoch < 0``: to nothing.  In place, so that a log
-    handler that has the file open for appending goes on behind the kept rows."""
+    handler that has the file open for appending goes on behind the kept rows.  ``rank_metrics.csv`` (a row every epoch,
+    the epoch first) is cut by the same rule."""
     if not os.path.isfile(path):
         return
     with open(path, "r+b") as f:

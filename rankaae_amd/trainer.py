@@ -20,6 +20,9 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
   ``spec_broaden`` a number s > 0 with ceil(3 s) <= 64 (default absent: off): every training step convolves each row of its
                 batch with a Gaussian of a random width of up to s grid points, on the device, before the shift and the
                 spectral noise; validation never broadens
+  ``rank_metrics`` true | false (default): every epoch's validation also forms Kendall's tau-b of each descriptor against
+                its style on the device, over the validation rows labelled for it, and rank 0 appends one row to
+                ``rank_metrics.csv`` (``Epoch,Tau_*,Labelled_*``); nothing else a run writes or returns changes
 
 Data parallel (the north star's replacement of the ipyparallel trial farm): started under
 ``torch.distributed.run`` (WORLD_SIZE > 1) every rank builds the same ``Trainer``; rank r steps rows
@@ -41,7 +44,7 @@ from .dataloader import get_dataloaders
 from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
 from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, ema_decay_of,
-                        grad_clip_norm_of, resume_on, spec_broaden_of, spec_shift_of)
+                        grad_clip_norm_of, rank_metrics_on, resume_on, spec_broaden_of, spec_shift_of)
 from . import resume as resume_file
 
 
@@ -136,6 +139,7 @@ class Trainer:
         self.spec_shift = spec_shift_of(cfg)
         self.spec_broaden = spec_broaden_of(cfg)
         self.detect_anomaly = detect_anomaly_on(cfg)
+        self.rank_metrics = rank_metrics_on(cfg)
         # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
         # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
         # the parity mode (its random tape is drawn from the global CPU generator in the reference's order)
@@ -334,10 +338,24 @@ class Trainer:
             self.logger.info(f"spec_shift: rows shifted by up to ±{self.spec_shift:g} grid points")
         if lead and self.spec_broaden is not None:
             self.logger.info(f"spec_broaden: rows broadened by a Gaussian of up to σ = {self.spec_broaden:g} grid points")
+        if lead and self.rank_metrics:
+            self.logger.info("rank_metrics: Kendall tau-b of every descriptor's style on the validation split, every epoch")
         best_chpt_file, metrics = None, None
         if lead and self.resume:
             # rows are written every 10 epochs and the run went on after its last resume file: back to that epoch
             resume_file.truncate_losses_csv(f"{self.work_dir}/losses.csv", st["epoch"] if st else resume_file.FRESH)
+        rank_csv = f"{self.work_dir}/rank_metrics.csv"
+        if lead and self.rank_metrics:
+            # one row per epoch, appended and closed (so flushed) every epoch.  A run from scratch starts the file; a
+            # resumed one cuts it back to the epoch it resumes from and goes on behind the kept rows -- or starts it
+            # there, where the earlier run did not have the key
+            if self.resume:
+                resume_file.truncate_losses_csv(rank_csv, st["epoch"] if st else resume_file.FRESH)
+            if not self.resume or not os.path.isfile(rank_csv) or os.path.getsize(rank_csv) == 0:
+                n_aux = eng.n_aux
+                with open(rank_csv, "w") as f:
+                    f.write(",".join(["Epoch"] + [f"Tau_{k}" for k in range(n_aux)] +
+                                     [f"Labelled_{k}" for k in range(n_aux)]) + "\n")
         if lead and not st:
             self.loss_logger.info(
                 "Epoch,Train_D,Val_D,Train_G,Val_G,Train_Aux,Val_Aux,Train_Recon,"
@@ -440,6 +458,10 @@ class Trainer:
             # (trainer.py:286-292), formed on the device by raae_style_metrics
             style_shapiro, style_rho = eng.val_style_metrics()
             style_coupling = np.max(np.fabs(style_rho))
+            if lead and self.rank_metrics:
+                tau, counts = eng.val_rank_metrics()
+                with open(rank_csv, "a") as f:
+                    f.write(",".join([f"{epoch:d}"] + [f"{t:.6f}" for t in tau] + [f"{int(m):d}" for m in counts[:, 5]]) + "\n")
             metrics = [float(np.min(style_shapiro)), vl["recon"], avg_mutual_info, float(style_coupling),
                        vl["kendall"]]
             metrics = broadcast_from_rank0(metrics, self.device, self.pg)     # no-op on one GPU
@@ -472,6 +494,9 @@ class Trainer:
                         ", ".join(f"{k} {vl[k]:.6f}" for k in ("adversarial", "kendall", "recon", "mutual_info", "smooth")) +
                         "; metrics (min Shapiro W, recon, validation mutual info, max |Spearman rho|, kendall) " +
                         ", ".join(f"{m:.6f}" for m in ema_metrics))
+                    if self.rank_metrics:
+                        self.logger.info("EMA rank metrics: Kendall tau-b per descriptor " +
+                                         ", ".join(f"{t:.6f}" for t in eng.val_rank_metrics()[0]))
                     torch.save(self._model_dict(), f"{self.work_dir}/final_ema.pt")
         if lead:
             if self.checkpoint_every and metrics is not None:

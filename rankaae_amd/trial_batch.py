@@ -70,6 +70,8 @@ class TrialBatch:
             if (e.spec_broaden is None) != (e0.spec_broaden is None):
                 # (the value may differ: every grid plane of raae_spec_augment2 reads its own largest sigma)
                 raise ValueError("the engines of a TrialBatch must agree on whether spec_broaden is set")
+            if e.rank_metrics != e0.rank_metrics:
+                raise ValueError("the engines of a TrialBatch must agree on rank_metrics")
             if not e.cfg.get("fused_step_begin", True) or not e.cfg.get("fused_discriminator", True):
                 raise ValueError("a TrialBatch needs the fused step head and the fused discriminator")
         self.engines, self.stream, self.T = list(engines), e0.stream, len(engines)
