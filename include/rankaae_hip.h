@@ -233,6 +233,24 @@ long raae_kendall_tau_work_bytes(int n, int n_aux);
 int raae_kendall_tau(const float* d, int ldd, const float* z, int ldz, int n, int n_aux, void* work, long long* counts,
                      double* tau, void* stream);
 
+/* Style decorrelation penalty (ABI 31; config key `style_decorr`): the mean squared off-diagonal Pearson correlation of
+ * the k style columns over the b rows,
+ *     D(z) = 1 / (k (k - 1)) * sum_{i != j} C_ij^2,   C_ij = u_i . u_j,   u_i = x_i / |x_i|,   x_i = z_i - mean(z_i),
+ * and its exact derivative, through the centring and the normalisation, ADDED to dz:
+ *     dz[r][i] = fl32(dz[r][i] + w * g[r][i]),   g[r][i] = 4 / (k (k - 1) s_i) * sum_{j != i} C_ij (u[r][j] - C_ij u[r][i]).
+ * z [b][ldz] styles, dz [b][lddz], 1 <= k <= 64, b >= 1, ldz >= k, lddz >= k, w finite (anything else: RAAE_EINVAL before
+ * a launch).  All arithmetic is double -- the means first, then the centred sums -- and the store of dz is the only fp32
+ * rounding; every sum has a fixed order and there are no atomics, so a repeated call gives the same bits.  A column
+ * whose centred sum of squares is exactly zero has C_i. = 0: it adds nothing to D and its dz elements are not written;
+ * b == 1 or k == 1 gives D = 0 and writes no dz; w == 0 writes no dz either.
+ *   stats: three doubles, written by one thread: [0] = D of this call, [1] += D, [2] += 1 (the caller zeroes [1], [2]).
+ *   work: >= raae_style_decorr_work_bytes(b, k) bytes (0 for a shape the call refuses); needs no initialisation.
+ * One launch where b * k <= 4096 (the styles fit one workgroup's LDS) or k == 1; otherwise two (per-chunk centred
+ * sums of min(256, 4096 / k) rows each, then their pairwise combination and the gradient); both forms batched. */
+long raae_style_decorr_work_bytes(int b, int k);
+int raae_style_decorr_fwd_bwd(const float* z, int ldz, int b, int k, double w, void* work, double* stats, float* dz,
+                              int lddz, void* stream);
+
 /* out[g][l] = mean over s of x[g][s][l], x [groups][per][L]: the n_sampling average of the report's decoder
  * sweeps (sc/report/analysis.py:78-86, `decoder(con_c).reshape(n_spec, n_sampling, L).mean(axis=1)`). */
 int raae_group_mean(const float* x, int groups, int per, int L, float* out, void* stream);
@@ -708,7 +726,7 @@ int raae_spec_augment2(const float* spec, const long* idx, const int* cursor, co
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2, since ABI 30 raae_kendall_tau) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2, since ABI 30 raae_kendall_tau, since ABI 31 raae_style_decorr_fwd_bwd) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -753,7 +771,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 30
+#define RAAE_ABI_VERSION 31
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

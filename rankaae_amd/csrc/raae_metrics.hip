@@ -9,6 +9,7 @@
 // Pearson correlation of the rank vectors.  All sums are double, in a fixed order (strided per thread, then a
 // tree), so a replay is bitwise repeatable.
 #include "raae_common.h"
+#include <cmath>
 
 namespace {
 
@@ -299,7 +300,239 @@ static int kendall_split(int T, int n_aux) {
     return s < 1 ? 1 : (s > kKtMaxSplit ? kKtMaxSplit : s);
 }
 
+// ---- style decorrelation penalty (ABI 31; config key `style_decorr`) ----------------------------------------------------
+// D(z) = 1 / (k (k - 1)) * sum_{i != j} C_ij^2, C the Pearson correlation matrix of the k style columns over the b rows,
+// and dz += w * dD/dz.  With x = z - mean, G = x^T x (the centred Gram matrix), s_i = sqrt(G_ii), C_ij = G_ij / (s_i s_j)
+// and q_i = sum_{j != i} C_ij^2 the exact derivative (through the centring and the normalisation) is one k x k matrix
+// applied to every centred row:
+//     dD/dz[r][i] = sum_j M_ij x[r][j],   M_ij = 4 C_ij / (k (k - 1) s_i s_j)  (i != j),   M_ii = -4 q_i / (k (k - 1) s_i^2)
+// A column with s_i == 0 has C_i. = 0 and a zero row and column of M: no gradient, nothing that is not finite.
+//
+// Everything is double: the means first, then the centred sums; the one fp32 rounding is the store of dz.  Every sum has
+// a fixed order (strided per thread, then the slices in index order), there are no atomics: a replay gives the same bits.
+// 256 threads; the k x k matrix, the per-column scalars and the workgroup's rows (as fp32) live in LDS, ~52 KB.
+//
+// One launch where the b * k styles fit the LDS stage (kDcStage floats: 256 x 6, 256 x 16, 64 x 64).  Otherwise two: the
+// rows are cut into chunks of min(256, kDcStage / k); decorr_chunk_kernel leaves every chunk's column sums, means and
+// Gram matrix centred on the CHUNK's means in `work`; every workgroup of decorr_apply_kernel then adds them as the
+// pairwise update of Chan, Golub and LeVeque does, G = sum_c G_c + n_c (m_c - m)(m_c - m)^T -- centred sums again, no
+// raw moments -- in chunk order (every workgroup the same bits), and applies M to its own chunk.
+constexpr int kDcStage = 4096;
+constexpr int kDcRows = 256;
+struct DecorrArgs {
+    const float* z; int ldz; int b; int k; double w; double* work; double* stats; float* dz; int lddz;
+    int rows; int nchunk;               // rows per workgroup (>= b: the one-launch form) and the number of workgroups
+};
+
+// rows [r0, r0 + n) of z -> zs [n][k]
+__device__ __forceinline__ void decorr_stage(const float* __restrict__ z, int ldz, int r0, int n, int k, float* zs) {
+    for (int e = threadIdx.x; e < n * k; e += 256) {
+        const int r = e / k, c = e - r * k;
+        zs[e] = z[(size_t)(r0 + r) * ldz + c];
+    }
+    __syncthreads();
+}
+
+// column sums, means and the Gram matrix centred on those means of the n staged rows.  A sum over the rows is cut into
+// as many slices as 256 threads allow (slice s takes rows s, s + nsl, ...); the slices meet in index order.
+__device__ __forceinline__ void decorr_chunk_stats(const float* zs, int n, int k, double* part, double* sum, double* mean,
+                                                   double* mat) {
+    const int tid = threadIdx.x;
+    {
+        const int nsl = 256 / k, sl = tid / k, c = tid - sl * k;
+        if (sl < nsl) {
+            double a = 0.0;
+            for (int r = sl; r < n; r += nsl) a += (double)zs[r * k + c];
+            part[sl * k + c] = a;
+        }
+        __syncthreads();
+        if (tid < k) {
+            double s = 0.0;
+            for (int q = 0; q < nsl; ++q) s += part[q * k + tid];
+            sum[tid] = s;
+            mean[tid] = s / (double)n;
+        }
+        __syncthreads();
+    }
+    const int P = k * k;
+    if (P <= 256) {
+        const int nsl = 256 / P, sl = tid / P, e = tid - sl * P;
+        if (sl < nsl) {
+            const int i = e / k, j = e - i * k;
+            const double mi = mean[i], mj = mean[j];
+            double a = 0.0;
+            for (int r = sl; r < n; r += nsl) a += ((double)zs[r * k + i] - mi) * ((double)zs[r * k + j] - mj);
+            part[sl * P + e] = a;
+        }
+        __syncthreads();
+        if (tid < P) {
+            double s = 0.0;
+            for (int q = 0; q < nsl; ++q) s += part[q * P + tid];
+            mat[tid] = s;
+        }
+    } else {
+        for (int e = tid; e < P; e += 256) {
+            const int i = e / k, j = e - i * k;
+            const double mi = mean[i], mj = mean[j];
+            double a = 0.0;
+            for (int r = 0; r < n; ++r) a += ((double)zs[r * k + i] - mi) * ((double)zs[r * k + j] - mj);
+            mat[e] = a;
+        }
+    }
+    __syncthreads();
+}
+
+// mat: G -> M in place (both symmetric); returns D in every thread.  sd, q: k doubles each.
+__device__ __forceinline__ double decorr_finish(double* mat, int k, double* sd, double* q) {
+    const int tid = threadIdx.x;
+    if (tid < k) sd[tid] = sqrt(mat[tid * k + tid]);
+    __syncthreads();
+    if (tid < k) {
+        const double si = sd[tid];
+        double a = 0.0;
+        for (int j = 0; j < k; ++j) {
+            const double sj = sd[j];
+            const double c = (j != tid && si > 0.0 && sj > 0.0) ? mat[tid * k + j] / (si * sj) : 0.0;
+            a += c * c;
+        }
+        q[tid] = a;
+    }
+    __syncthreads();
+    const double kk = (double)k * (double)(k - 1);
+    for (int e = tid; e < k * k; e += 256) {
+        const int i = e / k, j = e - i * k;
+        const double si = sd[i], sj = sd[j];
+        double m = 0.0;
+        if (si > 0.0 && sj > 0.0) m = i == j ? -4.0 * q[i] / (kk * si * si) : 4.0 * (mat[e] / (si * sj)) / (kk * si * sj);
+        mat[e] = m;
+    }
+    double D = 0.0;
+    for (int i = 0; i < k; ++i) D += q[i];
+    __syncthreads();
+    return D / kk;
+}
+
+// dz[r0 + r][i] = fl32(dz[r0 + r][i] + w * sum_j M_ij (zs[r][j] - mean[j])) for the n staged rows; an element whose
+// gradient is exactly zero (a constant column) is not written
+__device__ __forceinline__ void decorr_apply(const float* zs, int n, int k, const double* mat, const double* mean, double w,
+                                             float* __restrict__ dz, int lddz, int r0) {
+    for (int e = threadIdx.x; e < n * k; e += 256) {
+        const int r = e / k, i = e - r * k;
+        double g = 0.0;
+        for (int j = 0; j < k; ++j) g += mat[j * k + i] * ((double)zs[r * k + j] - mean[j]);
+        const double wg = w * g;
+        if (wg != 0.0) {
+            float* p = dz + (size_t)(r0 + r) * lddz + i;
+            *p = (float)((double)*p + wg);
+        }
+    }
+}
+
+__device__ __forceinline__ void decorr_write_stats(double* stats, double D) {
+    stats[0] = D;
+    stats[1] += D;
+    stats[2] += 1.0;
+}
+
+// the one-launch form: grid (1)
+__device__ __forceinline__ void decorr_one_body(const DecorrArgs& a) {
+    __shared__ double mat[64 * 64], part[256], sum[64], mean[64], sd[64], q[64];
+    __shared__ float zs[kDcStage];
+    if (a.k == 1 || a.b == 1) {                 // D = 0, no gradient (k == 1 comes here at every b: nothing is staged)
+        if (threadIdx.x == 0) decorr_write_stats(a.stats, 0.0);
+        return;
+    }
+    decorr_stage(a.z, a.ldz, 0, a.b, a.k, zs);
+    decorr_chunk_stats(zs, a.b, a.k, part, sum, mean, mat);
+    const double D = decorr_finish(mat, a.k, sd, q);
+    if (threadIdx.x == 0) decorr_write_stats(a.stats, D);
+    if (a.w != 0.0) decorr_apply(zs, a.b, a.k, mat, mean, a.w, a.dz, a.lddz, 0);
+}
+__global__ __launch_bounds__(256) void decorr_one_kernel(DecorrArgs a) { decorr_one_body(a); }
+__global__ __launch_bounds__(256) void decorr_one_kernel_m(const DecorrArgs* t) {
+    const DecorrArgs a = t[blockIdx.z];
+    decorr_one_body(a);
+}
+
+// the two-launch form, first launch: grid (nchunk); work [nchunk][k sums | k means | k * k Gram]
+__device__ __forceinline__ void decorr_chunk_body(const DecorrArgs& a) {
+    __shared__ double mat[64 * 64], part[256], sum[64], mean[64];
+    __shared__ float zs[kDcStage];
+    const int k = a.k, r0 = blockIdx.x * a.rows, n = min(a.rows, a.b - r0);
+    decorr_stage(a.z, a.ldz, r0, n, k, zs);
+    decorr_chunk_stats(zs, n, k, part, sum, mean, mat);
+    double* out = a.work + (size_t)blockIdx.x * (2 * k + k * k);
+    for (int e = threadIdx.x; e < k; e += 256) { out[e] = sum[e]; out[k + e] = mean[e]; }
+    for (int e = threadIdx.x; e < k * k; e += 256) out[2 * k + e] = mat[e];
+}
+__global__ __launch_bounds__(256) void decorr_chunk_kernel(DecorrArgs a) { decorr_chunk_body(a); }
+__global__ __launch_bounds__(256) void decorr_chunk_kernel_m(const DecorrArgs* t) {
+    const DecorrArgs a = t[blockIdx.z];
+    decorr_chunk_body(a);
+}
+
+// second launch: grid (nchunk)
+__device__ __forceinline__ void decorr_apply_body(const DecorrArgs& a) {
+    __shared__ double mat[64 * 64], mean[64], sd[64], q[64];
+    __shared__ float zs[kDcStage];
+    const int tid = threadIdx.x, k = a.k, r0 = blockIdx.x * a.rows, n = min(a.rows, a.b - r0);
+    const size_t stride = (size_t)(2 * k + k * k);
+    decorr_stage(a.z, a.ldz, r0, n, k, zs);
+    if (tid < k) {
+        double s = 0.0;
+        for (int c = 0; c < a.nchunk; ++c) s += a.work[c * stride + tid];
+        mean[tid] = s / (double)a.b;
+    }
+    __syncthreads();
+    for (int e = tid; e < k * k; e += 256) {
+        const int i = e / k, j = e - i * k;
+        const double mi = mean[i], mj = mean[j];
+        double g = 0.0;
+        for (int c = 0; c < a.nchunk; ++c) {
+            const double* wc = a.work + c * stride;
+            const double nc = (double)min(a.rows, a.b - c * a.rows);
+            g += wc[2 * k + e] + nc * ((wc[k + i] - mi) * (wc[k + j] - mj));
+        }
+        mat[e] = g;
+    }
+    __syncthreads();
+    const double D = decorr_finish(mat, k, sd, q);
+    if (blockIdx.x == 0 && tid == 0) decorr_write_stats(a.stats, D);
+    if (a.w != 0.0) decorr_apply(zs, n, k, mat, mean, a.w, a.dz, a.lddz, r0);
+}
+__global__ __launch_bounds__(256) void decorr_apply_kernel(DecorrArgs a) { decorr_apply_body(a); }
+__global__ __launch_bounds__(256) void decorr_apply_kernel_m(const DecorrArgs* t) {
+    const DecorrArgs a = t[blockIdx.z];
+    decorr_apply_body(a);
+}
+
+// rows per workgroup: b itself where one workgroup stages all of them
+static int decorr_rows(int b, int k) {
+    if (k == 1 || (long)b * k <= kDcStage) return b;
+    const int fit = kDcStage / k;
+    return fit < kDcRows ? fit : kDcRows;
+}
+
 }  // namespace
+
+extern "C" long raae_style_decorr_work_bytes(int b, int k) {
+    if (b < 1 || k < 1 || k > 64) return 0;
+    return (long)raae::cdiv(b, decorr_rows(b, k)) * (2 * k + k * k) * (long)sizeof(double);
+}
+
+extern "C" int raae_style_decorr_fwd_bwd(const float* z, int ldz, int b, int k, double w, void* work, double* stats, float* dz,
+                                         int lddz, void* stream) {
+    RAAE_CHECK_ARG(z && work && stats && dz && b >= 1 && k >= 1 && k <= 64 && ldz >= k && lddz >= k && std::isfinite(w));
+    const int rows = decorr_rows(b, k), nchunk = raae::cdiv(b, rows);
+    const DecorrArgs a = {z, ldz, b, k, w, (double*)work, stats, dz, lddz, rows, nchunk};
+    if (nchunk == 1) {
+        raae::launch(decorr_one_kernel, decorr_one_kernel_m, dim3(1), dim3(256), 0, (hipStream_t)stream, a);
+    } else {
+        raae::launch(decorr_chunk_kernel, decorr_chunk_kernel_m, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, a);
+        raae::launch(decorr_apply_kernel, decorr_apply_kernel_m, dim3(nchunk), dim3(256), 0, (hipStream_t)stream, a);
+    }
+    RAAE_LAUNCH_RET();
+}
 
 extern "C" long raae_kendall_tau_work_bytes(int n, int n_aux) {
     if (n < 1 || n_aux < 1 || n_aux > 16) return 0;

@@ -27,7 +27,7 @@ from . import _lib, ops, schedule
 from .metrics import KendallTau, StyleMetrics
 from .schedule import Pass
 from .parameter import (check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, rank_metrics_on,
-                        spec_broaden_of, spec_shift_of)
+                        spec_broaden_of, spec_shift_of, style_decorr_of)
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -480,6 +480,11 @@ class StepEngine:
         # build-only key `rank_metrics` (default false), checked likewise: every validation also forms Kendall's tau-b of
         # each descriptor against its style, two launches behind the style metrics (`validate`)
         self.rank_metrics = rank_metrics_on(cfg)
+        # build-only key `style_decorr` (default absent: off), checked likewise: phase B of every training step adds the
+        # gradient of w * D, D the mean squared off-diagonal correlation of the styles over the batch, to the rank
+        # loss's gradient -- one launch (two from 4096 / nstyle rows on) between the rank loss and the encoder backward
+        self.style_decorr = style_decorr_of(cfg)
+        self.decorr_stats = self._decorr_host = None
         if not torch.cuda.is_available():
             raise RuntimeError("rankaae_amd.engine needs an MI355X (no CPU/PyTorch fallback for the training path)")
         _lib.load()
@@ -522,6 +527,10 @@ class StepEngine:
             self.clip_partial = torch.zeros(n_opt, ops.GRAD_NORM_PARTS, dtype=torch.float64, device=device)
             self.clip_ticket = torch.zeros(n_opt, dtype=torch.int32, device=device)
         self._clip_host = None                # the counts as losses() read them; None once a step has been launched since
+        if self.style_decorr is not None:
+            # {D of the last step, sum of D, steps} since the last `style_decorr_stats(reset=True)`: written by the
+            # kernel's finishing thread inside the captured step, read back with losses()
+            self.decorr_stats = torch.zeros(3, dtype=torch.float64, device=device)
         if self.world_size > 1:
             import torch.distributed as dist
             self.comm_stream = torch.cuda.Stream(device=device)
@@ -892,6 +901,8 @@ class StepEngine:
             P.z_all = torch.empty(self.world_size * b, ns, device=dev)
             P.rank_totals = torch.zeros(80 if self.aux_missing else 64, dtype=torch.float64, device=dev)
         P.dstyles = torch.empty(b, ns, device=dev)
+        if self.style_decorr is not None:
+            P.decorr_work = torch.empty(ops.style_decorr_work_bytes(b, ns), dtype=torch.uint8, device=dev)
         P.dspec = torch.empty(b, self.L, device=dev)
         P.dout = torch.empty(b, self.L, device=dev)
         P.lpart = torch.zeros(RAAE_MAX_PARTS, dtype=torch.float64, device=dev)
@@ -1194,6 +1205,10 @@ class StepEngine:
         else:
             styles = enc.forward(E, P.spec, P.m_enc[1])
         self._rank_loss(P, styles)
+        if self.style_decorr is not None:
+            # `style_decorr`: dstyles += w * dD/dstyles over this rank's own rows (data parallel: no collective, and no
+            # factor W with `rank_loss_pairs: global` -- the ranks' penalties are averaged with the gradients)
+            ops.style_decorr(styles, ns, b, ns, self.style_decorr, P.decorr_work, self.decorr_stats, P.dstyles, ns)
         enc.backward(E, P.spec, P.m_enc[1], P.dstyles)
         self._adam(P, "correlation", self._slab_notes)
         # ---- phase C: reconstruction (:164-172)
@@ -1272,6 +1287,7 @@ class StepEngine:
         P = self.plan(b)
         self._nan_host = None
         self._clip_host = None
+        self._decorr_host = None
         stride = self.cursor_stride if self.cursor_stride is not None else b
         if self._host_cursor + b > len(self.train_spec):
             raise RuntimeError(f"epoch exhausted: rows [{self._host_cursor}, {self._host_cursor + b}) exceed the "
@@ -1461,7 +1477,25 @@ class StepEngine:
         v = words[:8].view(torch.float32).tolist()
         if self.grad_clip is not None:        # (only with the key set: the counts of clipped steps)
             self._clip_host = self.clip_counts.tolist()
+        if self.style_decorr is not None:     # (likewise: the penalty's running sum and step count)
+            self._decorr_host = self.decorr_stats.tolist()
         return {k: v[i] for k, i in LOSS_SLOTS.items()}
+
+    @_on_stream
+    def style_decorr_stats(self, reset=True):
+        """``style_decorr``: ``(mean D, steps)`` over the training steps since the last reset -- ``D`` the mean squared
+        off-diagonal correlation of the phase-B styles over the batch; ``(nan, 0)`` before the first step.  Uses what
+        the last ``losses()`` read when no step has been launched since (no extra synchronisation at the epoch
+        boundary); otherwise reads the sums now.  ``reset``: start a new average.  ``RuntimeError`` on an engine
+        without the key."""
+        if self.style_decorr is None:
+            raise RuntimeError("style_decorr_stats(): this engine adds no decorrelation penalty (config key style_decorr)")
+        host = self._decorr_host if self._decorr_host is not None else self.decorr_stats.tolist()
+        if reset:
+            self.decorr_stats[1:].zero_()
+            self._decorr_host = None
+        steps = int(host[2])
+        return (host[1] / steps if steps else float("nan")), steps
 
     @_on_stream
     def clipped_steps(self):
@@ -1569,6 +1603,9 @@ class StepEngine:
         self.seed = int(state["seed"])
         self._nan_host = None
         self._clip_host = None
+        self._decorr_host = None
+        if self.decorr_stats is not None:       # (`style_decorr`: the epoch's sums start at zero; a state carries none)
+            self.decorr_stats.zero_()
         torch.cuda.current_stream().synchronize()      # the host tensors of `state` may go once this returns
 
     @_on_stream

@@ -263,6 +263,20 @@ def kendall_tau(d, ldd, z, ldz, n, n_aux, work, counts, tau):
                                        _ptr(tau, torch.float64), _stream()), "raae_kendall_tau")
 
 
+def style_decorr_work_bytes(b, k):
+    return int(_lib.load().raae_style_decorr_work_bytes(b, k))
+
+
+def style_decorr(z, ldz, b, k, w, work, stats, dz, lddz):
+    """The decorrelation penalty of the styles ``z [b, >= k]`` (``raae_style_decorr_fwd_bwd``): ``dz += w * dD/dz`` in
+    place, ``stats`` float64 ``[3]`` = {D, running sum of D, calls}, ``work`` a byte buffer of
+    ``style_decorr_work_bytes``.  One launch where ``b * k <= 4096``, two otherwise; no host synchronisation."""
+    assert z.numel() >= (b - 1) * ldz + k and dz.numel() >= (b - 1) * lddz + k and stats.numel() >= 3
+    assert work.numel() * work.element_size() >= style_decorr_work_bytes(b, k) > 0
+    check(_lib.load().raae_style_decorr_fwd_bwd(_ptr(z), ldz, b, k, float(w), _ptr(work, None), _ptr(stats, torch.float64),
+                                                _ptr(dz), lddz, _stream()), "raae_style_decorr_fwd_bwd")
+
+
 def group_mean(x, groups, per, L, out):
     check(_lib.load().raae_group_mean(_ptr(x), groups, per, L, _ptr(out), _stream()), "raae_group_mean")
 

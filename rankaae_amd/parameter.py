@@ -110,6 +110,20 @@ def spec_broaden_of(cfg, rng_mode=None):
     return float(value)
 
 
+def style_decorr_of(cfg):
+    """Build-only key ``style_decorr`` (default absent / ``null``: off): a finite float ``w > 0``, the weight of the
+    decorrelation penalty.  Phase B of every training step then minimises ``aux_loss + w * D``, ``D`` the mean squared
+    off-diagonal Pearson correlation of the styles over the batch: ``w * dD/dstyles`` is added to the rank loss's
+    gradient on the device (``raae_style_decorr_fwd_bwd``) before the encoder's backward pass.  ``D`` enters no logged
+    loss; ``w`` scales the gradient, not the learning rate.  Returns the float, or None."""
+    value = cfg.get("style_decorr", None)
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < float("inf")):
+        raise ValueError(f"style_decorr must be absent, null or a finite number > 0, not {value!r}")
+    return float(value)
+
+
 REPORT_WEIGHTS = {"final": "final.pt", "ema": "final_ema.pt"}
 
 

@@ -115,6 +115,10 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     # `spec_broaden` likewise
     if cfg.get("spec_broaden") is not None:
         fp["cfg.spec_broaden"] = float(cfg["spec_broaden"])
+    # `style_decorr` likewise: a run with another weight would continue on another phase-B gradient (its per-epoch
+    # statistics are reset at every epoch boundary: the file carries nothing of them)
+    if cfg.get("style_decorr") is not None:
+        fp["cfg.style_decorr"] = float(cfg["style_decorr"])
     # (`rank_metrics` stays out: it adds a file beside the run and shapes nothing of the training, so a run may be
     # resumed with the key turned on or off)
     spec = np.asarray(train_spec, dtype=np.float64)

@@ -23,6 +23,9 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
   ``rank_metrics`` true | false (default): every epoch's validation also forms Kendall's tau-b of each descriptor against
                 its style on the device, over the validation rows labelled for it, and rank 0 appends one row to
                 ``rank_metrics.csv`` (``Epoch,Tau_*,Labelled_*``); nothing else a run writes or returns changes
+  ``style_decorr`` a number w > 0 (default absent: off): phase B of every training step minimises ``aux_loss + w * D``, ``D``
+                the mean squared off-diagonal Pearson correlation of the styles over the batch (its exact gradient is added
+                on the device); one ``messages.txt`` line per epoch with the epoch's mean ``D``; no logged loss changes
 
 Data parallel (the north star's replacement of the ipyparallel trial farm): started under
 ``torch.distributed.run`` (WORLD_SIZE > 1) every rank builds the same ``Trainer``; rank r steps rows
@@ -44,7 +47,7 @@ from .dataloader import get_dataloaders
 from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
 from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, ema_decay_of,
-                        grad_clip_norm_of, rank_metrics_on, resume_on, spec_broaden_of, spec_shift_of)
+                        grad_clip_norm_of, rank_metrics_on, resume_on, spec_broaden_of, spec_shift_of, style_decorr_of)
 from . import resume as resume_file
 
 
@@ -140,6 +143,7 @@ class Trainer:
         self.spec_broaden = spec_broaden_of(cfg)
         self.detect_anomaly = detect_anomaly_on(cfg)
         self.rank_metrics = rank_metrics_on(cfg)
+        self.style_decorr = style_decorr_of(cfg)
         # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
         # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
         # the parity mode (its random tape is drawn from the global CPU generator in the reference's order)
@@ -338,6 +342,9 @@ class Trainer:
             self.logger.info(f"spec_shift: rows shifted by up to ±{self.spec_shift:g} grid points")
         if lead and self.spec_broaden is not None:
             self.logger.info(f"spec_broaden: rows broadened by a Gaussian of up to σ = {self.spec_broaden:g} grid points")
+        if lead and self.style_decorr is not None:
+            self.logger.info(f"style_decorr: w = {self.style_decorr:g} (phase B minimises aux_loss + w * D, D the mean "
+                             "squared off-diagonal correlation of the styles over the batch)")
         if lead and self.rank_metrics:
             self.logger.info("rank_metrics: Kendall tau-b of every descriptor's style on the validation split, every epoch")
         best_chpt_file, metrics = None, None
@@ -439,6 +446,12 @@ class Trainer:
                         f"{name} clipped {k - k0} of {n} steps"
                         for name, k, k0, n in zip(OPT_NAMES, clipped, clipped_before, steps)))
                 clipped_before = clipped
+            if self.style_decorr is not None:
+                # (read by losses(), like the anomaly flags; the sums start again with every epoch.  Data parallel: each
+                # rank penalises its own rows, the line is rank 0's mean)
+                d_mean, d_steps = eng.style_decorr_stats(reset=True)
+                if lead:
+                    self.logger.info(f"Epoch {epoch}: style_decorr: mean D = {d_mean:.6f} over {d_steps} steps")
             if not smooth:
                 tl["smooth"] = 0.0
             if self.world > 1:

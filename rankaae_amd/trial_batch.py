@@ -70,6 +70,9 @@ class TrialBatch:
             if (e.spec_broaden is None) != (e0.spec_broaden is None):
                 # (the value may differ: every grid plane of raae_spec_augment2 reads its own largest sigma)
                 raise ValueError("the engines of a TrialBatch must agree on whether spec_broaden is set")
+            if (e.style_decorr is None) != (e0.style_decorr is None):
+                # (the value may differ: every grid plane of raae_style_decorr_fwd_bwd reads its own weight)
+                raise ValueError("the engines of a TrialBatch must agree on whether style_decorr is set")
             if e.rank_metrics != e0.rank_metrics:
                 raise ValueError("the engines of a TrialBatch must agree on rank_metrics")
             if not e.cfg.get("fused_step_begin", True) or not e.cfg.get("fused_discriminator", True):
