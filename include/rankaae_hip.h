@@ -171,6 +171,30 @@ long raae_rank_loss_masked_work_bytes(int B, int n_aux);
 int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
                                   void* work, float* loss, float* dz, void* stream);
 
+/* The pairwise logistic (RankNet) form of the rank loss (ABI 32; config key `rank_loss_form: logistic`).  S_k is the set
+ * of rows whose descriptor k is finite (a NaN cell is a missing label), m_k their number, T the temperature, and with
+ *     s_ij = sign(d_ik - d_jk),   x_ij = -s_ij (z_ik - z_jk) / T:
+ *     loss     = (1 / n_aux) sum_k T / max(m_k^2 - m_k, 1) sum_{i,j in S_k, s_ij != 0} softplus(x_ij)
+ *     dz[i][k] = -2 / (n_aux max(m_k^2 - m_k, 1)) sum_{j in S_k, s_ij != 0} s_ij sigma(x_ij)
+ * -- the normalisation of raae_rank_loss_masked_fwd_bwd; the factor T makes the limit T -> 0+ the hinge max(0, -s dz),
+ * whose gradient on a misordered pair is the linear loss's.  The loss is >= 0.  A descriptor with m_k < 2 contributes 0,
+ * tied descriptors contribute nothing, equal styles with distinct descriptors contribute ln 2 and sigma = 1/2 (the
+ * linear kernels drop such a pair).  dz [B][lddz] is OVERWRITTEN: a zero for every i outside S_k and in the columns
+ * >= n_aux; nothing is NaN or Inf for finite z, whatever (z_i - z_j) / T is.
+ * One form for fully and partly labelled data.  `temperature` is cast to fp32 once and that value is the T of every
+ * pair and of the loss.  Per pair in fp32, each operation rounded once: the difference, the IEEE divide by T,
+ * e = expf(-|x|), sigma = (x >= 0 ? 1 : e) / (1 + e), softplus = max(x, 0) + log1pf(e).  A lane adds its terms in fp32
+ * over at most ceil(B / 8) columns; everything across lanes and workgroups of the loss is added in double; the
+ * gradient's column-block partials are added in block order.  No atomics, fixed summation order: a repeated call gives
+ * the same bits.  Two launches (pair pass on raae_rank_loss_fwd_bwd's grid, finish), both with the batched (gridDim.z)
+ * form; every plane reads its own temperature.
+ * RAAE_EINVAL before any launch: B < 2, n_aux outside 1..16, ldd, ldz or lddz < n_aux, a null pointer, a temperature
+ * that is not finite and > 0 (as an fp32 value).
+ *   work: >= raae_rank_logistic_work_bytes(B, n_aux) bytes (0 for a shape the call refuses); needs no initialisation. */
+long raae_rank_logistic_work_bytes(int B, int n_aux);
+int raae_rank_logistic_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, double temperature,
+                               void* work, float* loss, float* dz, int lddz, void* stream);
+
 /* The same loss over the GLOBAL pairs of a data-parallel batch (what sc/utils/functions.py:63-77 computes on the
  * whole batch in one process), split per rank: this rank owns rows [row0, row0 + nrows) of the all-gathered
  * d_all / z_all [n_all][ld] and pairs them with all n_all rows.
@@ -726,7 +750,7 @@ int raae_spec_augment2(const float* spec, const long* idx, const int* cursor, co
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2, since ABI 30 raae_kendall_tau, since ABI 31 raae_style_decorr_fwd_bwd) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2, since ABI 30 raae_kendall_tau, since ABI 31 raae_style_decorr_fwd_bwd, since ABI 32 raae_rank_logistic_fwd_bwd) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -771,7 +795,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 31
+#define RAAE_ABI_VERSION 32
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -515,6 +515,165 @@ __global__ __launch_bounds__(256) void rank_rows_masked_finalize_kernel_m(const 
     rank_rows_masked_finalize_body(a);
 }
 
+// ------------------------------------------------------------------ logistic rank loss (config key rank_loss_form)
+// The pairwise logistic (RankNet) form of the rank loss: with s = sign(d_ik - d_jk), x = -s (z_ik - z_jk) / T,
+//   loss = (1 / KA) sum_k T / norm_k sum_{i,j in S_k, s != 0} softplus(x),  dz_ik = -2 / (KA norm_k) sum_j s sigma(x),
+// S_k the rows labelled for k, norm_k = max(m_k^2 - m_k, 1) as in the masked linear form.  One form for labelled and
+// partly labelled data: the label test is two bit operations beside an exp, a log and a divide per pair.
+// rank_pairs_body's structure and rank_grid's geometry: a thread owns (row, descriptor, j-chunk) and R rows, the j rows
+// stream through LDS tiles, the 8 chunk lanes meet through xor shuffles, column blocks leave per-block partial
+// gradients.  Per pair, all fp32 and each operation rounded once: the difference, the IEEE divide by T, expf of
+// -|x| (never overflows), sigma = (x >= 0 ? 1 : e) / (1 + e), softplus = max(x, 0) + log1pf(e).  A lane's loss terms are
+// added in fp32 over its columns only, then in double across lanes, row groups and workgroups.  No atomics.
+struct RankLogArgs { const float* d; int ldd; const float* z; int ldz; int B; int nj; int jchunk; float T;
+                     double* lossp; int* lab; float* g; };
+template <int KA, int R>
+__device__ __forceinline__ void rank_logistic_body(const RankLogArgs& a) {
+    constexpr int IPB = 32 / KA;            // (row, k) slots per block = IPB * KA <= 32
+    __shared__ float sd[RANK_TJ * KA], sz[RANK_TJ * KA];
+    __shared__ double red_s[32];
+    __shared__ int red_l[32];
+    const int tid = threadIdx.x, c = tid & (RANK_JC - 1), q = tid >> 3;
+    const int il = q / KA, k = q - il * KA;
+    const bool slot = il < IPB;
+    const int B = a.B;
+    const float T = a.T;
+    double tls = 0.0;                       // block totals of this (il, k) slot over all its row groups
+    int tlab = 0;
+    const int rows_per_group = IPB * R;
+    const int ngroups = (B + rows_per_group - 1) / rows_per_group;
+    const int jb = blockIdx.x % a.nj, ib = blockIdx.x / a.nj, ni_wg = gridDim.x / a.nj;
+    const int jlo = jb * a.jchunk, jhi = min(B, jlo + a.jchunk);
+    for (int grp = ib; grp < ngroups; grp += ni_wg) {
+        float di[R], zi[R], gs[R], ls[R];
+        int irow[R];
+        bool vi[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            irow[r] = grp * rows_per_group + r * IPB + il;
+            const bool ok = slot && irow[r] < B;
+            di[r] = ok ? a.d[(size_t)irow[r] * a.ldd + k] : 0.f;
+            zi[r] = ok ? a.z[(size_t)irow[r] * a.ldz + k] : 0.f;
+            gs[r] = ls[r] = 0.f;
+            vi[r] = ok && rank_labelled(di[r]);             // (a row beyond B pairs with nothing)
+            if (vi[r] && c == 0 && jb == 0) ++tlab;
+        }
+        for (int j0 = jlo; j0 < jhi; j0 += RANK_TJ) {
+            const int ntile = min(RANK_TJ, jhi - j0);
+            __syncthreads();
+            for (int idx = tid; idx < ntile * KA; idx += 256) {
+                const int jj = idx / KA, kk = idx - jj * KA;
+                sd[idx] = a.d[(size_t)(j0 + jj) * a.ldd + kk];
+                sz[idx] = a.z[(size_t)(j0 + jj) * a.ldz + kk];
+            }
+            __syncthreads();
+            if (slot) {
+                for (int jj = c; jj < ntile; jj += RANK_JC) {
+                    const float dj = sd[jj * KA + k], zj = sz[jj * KA + k];
+                    const bool vj = rank_labelled(dj);
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const float dd = di[r] - dj;
+                        const bool on = vi[r] && vj && dd != 0.f;       // (a tie pairs with nothing)
+                        const float del = zi[r] - zj;
+                        const float x = (dd > 0.f ? -del : del) / T;
+                        const float e = expf(-fabsf(x));
+                        const float sig = (x >= 0.f ? 1.f : e) / (1.f + e);
+                        const float sp = fmaxf(x, 0.f) + log1pf(e);
+                        gs[r] += on ? (dd > 0.f ? sig : -sig) : 0.f;
+                        ls[r] += on ? sp : 0.f;
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float g = gs[r];
+            double l = (double)ls[r];
+#pragma unroll
+            for (int o = 1; o < RANK_JC; o <<= 1) { g += __shfl_xor(g, o, 64); l += __shfl_xor(l, o, 64); }
+            if (slot && irow[r] < B && c == 0) {
+                a.g[((size_t)jb * B + irow[r]) * KA + k] = g;
+                tls += l;
+            }
+        }
+    }
+    // block totals per k: slots (il, k) combine in fixed order
+    __syncthreads();
+    if (c == 0) { red_s[q] = tls; red_l[q] = tlab; }
+    __syncthreads();
+    if (tid < KA) {
+        double s = 0.0; int m = 0;
+        for (int i2 = 0; i2 < IPB; ++i2) { s += red_s[i2 * KA + tid]; m += red_l[i2 * KA + tid]; }
+        a.lossp[(size_t)blockIdx.x * RANK_MAXK + tid] = s;
+        a.lab[(size_t)blockIdx.x * RANK_MAXK + tid] = m;
+    }
+}
+template <int KA, int R>
+__global__ __launch_bounds__(256) void rank_logistic_kernel(RankLogArgs a) { rank_logistic_body<KA, R>(a); }
+template <int KA, int R>
+__global__ __launch_bounds__(256) void rank_logistic_kernel_m(const RankLogArgs* t) {
+    const RankLogArgs a = t[blockIdx.z];
+    rank_logistic_body<KA, R>(a);
+}
+
+// finish: every workgroup re-derives m_k, norm_k and the loss from the partials (16 slices per descriptor, fixed
+// order), then grid-strides over dz [B][lddz]: the column blocks' partial gradients in block order, zeros in the
+// columns >= KA.  An unlabelled row's partials are zeros, so its dz is a zero; m_k < 2 has no pair, so its term is 0.
+struct RankLogFinArgs { const double* lossp; const int* lab; int nparts; int B; int nj; int KA; float T; const float* g;
+                        float* loss; float* dz; int lddz; };
+__device__ __forceinline__ void rank_logistic_finish_body(const RankLogFinArgs& a) {
+    __shared__ float s_f[RANK_MAXK];
+    __shared__ double s_loss[RANK_MAXK];
+    __shared__ double r_s[256];
+    __shared__ long long r_n[256];
+    const int tid = threadIdx.x, KA = a.KA;
+    {
+        const int k = tid & 15, sl = tid >> 4;          // 16 slices
+        long long m = 0; double s = 0.0;
+        if (k < KA) {
+#pragma unroll 8
+            for (int p = sl; p < a.nparts; p += 16) {
+                s += a.lossp[(size_t)p * RANK_MAXK + k];
+                m += a.lab[(size_t)p * RANK_MAXK + k];
+            }
+        }
+        r_s[tid] = s; r_n[tid] = m;
+    }
+    __syncthreads();
+    if (tid < KA) {
+        long long m = 0; double s = 0.0;
+        for (int sl = 0; sl < 16; ++sl) { s += r_s[sl * 16 + tid]; m += r_n[sl * 16 + tid]; }
+        const double pairs = (double)m * (double)m - (double)m;
+        const double norm = (pairs > 1.0 ? pairs : 1.0) * (double)KA;
+        s_f[tid] = (float)(-2.0 / norm);
+        s_loss[tid] = s / norm;
+    }
+    __syncthreads();
+    if (blockIdx.x == 0 && tid == 0) {
+        double t = 0.0;
+        for (int k = 0; k < KA; ++k) t += s_loss[k];
+        a.loss[0] = (float)(t * (double)a.T);
+    }
+    const long n = (long)a.B * a.lddz;
+    const size_t blk = (size_t)a.B * KA;
+    for (long idx = (long)blockIdx.x * 256 + tid; idx < n; idx += (long)gridDim.x * 256) {
+        const int i = (int)(idx / a.lddz), k = (int)(idx - (long)i * a.lddz);
+        float v = 0.f;
+        if (k < KA) {
+            float g = 0.f;
+            for (int b = 0; b < a.nj; ++b) g += a.g[b * blk + (size_t)i * KA + k];
+            v = s_f[k] * g;
+        }
+        a.dz[idx] = v;
+    }
+}
+__global__ __launch_bounds__(256) void rank_logistic_finish_kernel(RankLogFinArgs a) { rank_logistic_finish_body(a); }
+__global__ __launch_bounds__(256) void rank_logistic_finish_kernel_m(const RankLogFinArgs* t) {
+    const RankLogFinArgs a = t[blockIdx.z];
+    rank_logistic_finish_body(a);
+}
+
 // ------------------------------------------------------------------ reconstruction loss
 // functions.py:81-107.  One wave per row; L <= 1024.
 // Optional finalisation inside the loss kernel: after thread 0 has stored this workgroup's partial, the LAST workgroup
@@ -898,6 +1057,45 @@ extern "C" int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const floa
     const int gf = dz ? grid_for((long)B * ldz, 256, 256) : 1;
     const RankMaskedFinArgs fa = {(const RankWork*)work, labelled, g.nwg, B, g.nj, n_aux, activate, gpos, gneg, loss, dz, ldz};
     raae::launch(rank_masked_finalize_kernel, rank_masked_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
+    RAAE_LAUNCH_RET();
+}
+
+// The logistic rank loss: work = loss partials [RANK_MAXWG][16] doubles, labelled-row counts [RANK_MAXWG][16] ints, the
+// column blocks' partial gradients [RANK_MAXNJ][B][n_aux] floats.  Every word that the finish reads the pair pass has
+// written, so the buffer needs no initialisation.
+static size_t rank_logistic_lossp_bytes() { return (size_t)RANK_MAXWG * RANK_MAXK * sizeof(double); }
+static size_t rank_logistic_lab_bytes() { return (size_t)RANK_MAXWG * RANK_MAXK * sizeof(int); }
+extern "C" long raae_rank_logistic_work_bytes(int B, int n_aux) {
+    if (B < 2 || n_aux < 1 || n_aux > RANK_MAXK) return 0;
+    return (long)(rank_logistic_lossp_bytes() + rank_logistic_lab_bytes() + (size_t)RANK_MAXNJ * B * n_aux * sizeof(float));
+}
+
+extern "C" int raae_rank_logistic_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux,
+                                          double temperature, void* work, float* loss, float* dz, int lddz, void* stream) {
+    RAAE_CHECK_ARG(d && z && work && loss && dz && B > 1 && n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux &&
+                   ldz >= n_aux && lddz >= n_aux);
+    const float T = (float)temperature;                     // the one cast: every pair and the loss use this value
+    RAAE_CHECK_ARG(temperature > 0.0 && T > 0.f && T <= 3.402823466e38f);       // (NaN fails the first comparison)
+    hipStream_t st = (hipStream_t)stream;
+    const RankGrid g = rank_grid(B, B, n_aux);
+    double* lossp = (double*)work;
+    int* lab = (int*)((char*)work + rank_logistic_lossp_bytes());
+    float* gpart = (float*)((char*)work + rank_logistic_lossp_bytes() + rank_logistic_lab_bytes());
+    const RankLogArgs pa = {d, ldd, z, ldz, B, g.nj, g.jchunk, T, lossp, lab, gpart};
+#define RANK_CASE(KA) case KA: \
+        if (g.R == 1) raae::launch(rank_logistic_kernel<KA, 1>, rank_logistic_kernel_m<KA, 1>, dim3(g.nwg), dim3(256), 0, st, pa); \
+        else raae::launch(rank_logistic_kernel<KA, 4>, rank_logistic_kernel_m<KA, 4>, dim3(g.nwg), dim3(256), 0, st, pa); \
+        break;
+    switch (n_aux) {
+        RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
+        RANK_CASE(9) RANK_CASE(10) RANK_CASE(11) RANK_CASE(12) RANK_CASE(13) RANK_CASE(14) RANK_CASE(15) RANK_CASE(16)
+        default: return RAAE_EINVAL;
+    }
+#undef RANK_CASE
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    const RankLogFinArgs fa = {lossp, lab, g.nwg, B, g.nj, n_aux, T, gpart, loss, dz, lddz};
+    raae::launch(rank_logistic_finish_kernel, rank_logistic_finish_kernel_m, dim3(grid_for((long)B * lddz, 256, 256)), dim3(256), 0, st, fa);
     RAAE_LAUNCH_RET();
 }
 

@@ -26,8 +26,8 @@ from torch import nn
 from . import _lib, ops, schedule
 from .metrics import KendallTau, StyleMetrics
 from .schedule import Pass
-from .parameter import (check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, rank_metrics_on,
-                        spec_broaden_of, spec_shift_of, style_decorr_of)
+from .parameter import (check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, rank_loss_form_of,
+                        rank_metrics_on, spec_broaden_of, spec_shift_of, style_decorr_of)
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -485,6 +485,9 @@ class StepEngine:
         # loss's gradient -- one launch (two from 4096 / nstyle rows on) between the rank loss and the encoder backward
         self.style_decorr = style_decorr_of(cfg)
         self.decorr_stats = self._decorr_host = None
+        # build-only keys `rank_loss_form` / `rank_temperature` (default linear), checked likewise: with `logistic` phase
+        # B's loss and gradient are the pairwise logistic loss's (`_rank_loss`); the validation pass keeps the linear one
+        self.rank_loss_form, self.rank_temperature = rank_loss_form_of(cfg, int(world_size))
         if not torch.cuda.is_available():
             raise RuntimeError("rankaae_amd.engine needs an MI355X (no CPU/PyTorch fallback for the training path)")
         _lib.load()
@@ -895,7 +898,8 @@ class StepEngine:
         if self.spec_broaden is not None:
             # the width of row b is drawn at SPEC_BROADEN_OFF + b: beyond every dropout element and every shift draw
             assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF and b < 2 ** 30
-        P.rank_work = torch.empty(self._rank_work_bytes(b, rows_form=self.rank_pairs_global), dtype=torch.uint8, device=dev)
+        P.rank_work = torch.empty(self._rank_work_bytes(b, rows_form=self.rank_pairs_global, train=True), dtype=torch.uint8,
+                                  device=dev)
         if self.rank_pairs_global:
             P.aux_all = torch.empty(self.world_size * b, self.n_aux, device=dev)
             P.z_all = torch.empty(self.world_size * b, ns, device=dev)
@@ -1048,8 +1052,11 @@ class StepEngine:
         else:
             self._cut(lambda: self._run_comm(kind, bufs))
 
-    def _rank_work_bytes(self, rows, rows_form=False):
-        """``rows_form``: the buffer of a rows-against-all pair over ``rows`` of this rank's rows."""
+    def _rank_work_bytes(self, rows, rows_form=False, train=False):
+        """``rows_form``: the buffer of a rows-against-all pair over ``rows`` of this rank's rows.  ``train``: the
+        buffer of a training step, whose loss follows ``rank_loss_form`` (validation is always the linear loss)."""
+        if train and self.rank_loss_form == "logistic":
+            return ops.rank_logistic_work_bytes(rows, self.n_aux)
         if self.aux_missing:
             return (ops.rank_rows_masked_work_bytes if rows_form else ops.rank_loss_masked_work_bytes)(rows, self.n_aux)
         return ops.rank_loss_work_bytes(rows, self.n_aux)
@@ -1062,6 +1069,12 @@ class StepEngine:
         (``aux_missing``): the masked kernels; with global pairs the all-reduce also carries the per-descriptor
         labelled-row counts (640 bytes), so every rank normalises by the labelled pairs of the whole batch."""
         c, b, ns, lo = self.cfg, P.b, self.nstyle, self.loss_out
+        if self.rank_loss_form == "logistic":
+            # `rank_loss_form: logistic`: one kernel for labelled and partly labelled data, over this rank's own rows
+            # (global pairs are refused at construction); `kendall_activation` does not apply, the sigmoid is the weight
+            ops.rank_logistic_fwd_bwd(P.aux, self.n_aux, styles, ns, b, self.n_aux, self.rank_temperature, P.rank_work,
+                                      lo[1:2], P.dstyles, ns)
+            return
         if not self.rank_pairs_global:
             # (missing labels: rows without a label for descriptor k leave its pairs)
             fwd_bwd = ops.rank_loss_masked_fwd_bwd if self.aux_missing else ops.rank_loss_fwd_bwd

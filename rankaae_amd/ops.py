@@ -213,6 +213,21 @@ def rank_loss_masked_fwd_bwd(d, ldd, z, ldz, B, n_aux, activate, work, loss, dz)
     _probed("rank_pairs_masked_kernel", 4 * B * n_aux * 3, launch)
 
 
+def rank_logistic_work_bytes(B, n_aux):
+    return int(_lib.load().raae_rank_logistic_work_bytes(B, n_aux))
+
+
+def rank_logistic_fwd_bwd(d, ldd, z, ldz, B, n_aux, temperature, work, loss, dz, lddz):
+    """The pairwise logistic rank loss (``raae_rank_logistic_fwd_bwd``): ``loss[0]`` and ``dz [B, lddz]`` (overwritten)
+    from the descriptors ``d`` (NaN cells are missing labels) and the styles ``z``; ``work`` a byte buffer of
+    ``rank_logistic_work_bytes``.  Two launches; no host synchronisation."""
+    def launch():
+        check(_lib.load().raae_rank_logistic_fwd_bwd(_ptr(d), ldd, _ptr(z), ldz, B, n_aux, float(temperature),
+                                                     _ptr(work, None), _ptr(loss), _ptr(dz), lddz, _stream()),
+              "raae_rank_logistic_fwd_bwd")
+    _probed("rank_logistic_kernel", 4 * B * n_aux * 3, launch)
+
+
 def rank_rows_pairs(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, work, totals):
     check(_lib.load().raae_rank_rows_pairs(_ptr(d_all), ldd, _ptr(z_all), ldz, n_all, row0, nrows, n_aux, _ptr(work, None),
                                            _ptr(totals, torch.float64), _stream()), "raae_rank_rows_pairs")

@@ -124,6 +124,40 @@ def style_decorr_of(cfg):
     return float(value)
 
 
+RANK_LOSS_FORMS = ("linear", "logistic")
+
+
+def rank_loss_form_of(cfg, world_size=1):
+    """Build-only keys ``rank_loss_form`` (``linear``, the default: the reference's ``kendall_constraint``; or
+    ``logistic``) and ``rank_temperature`` (a finite float ``T > 0``, default 1.0, with ``logistic`` only).  With
+    ``logistic`` phase B of every training step minimises the pairwise logistic (RankNet) loss
+    ``T * softplus(-s * (z_i - z_j) / T)`` over the pairs with distinct labelled descriptors (``s`` the sign of the
+    descriptor difference), normalised like the linear loss (``raae_rank_logistic_fwd_bwd``): the gradient of a pair is
+    the sigmoid of how wrongly it is ordered, the loss is bounded below by 0, and ``kendall_activation`` is not applied
+    to it.  The styles leave the style BatchNorm with unit variance, so ``T`` is in style standard deviations; the
+    default 1.0 is a convention, not a tuned value.  The validation pass keeps the linear loss.  ``world_size > 1``
+    with ``rank_loss_pairs: global`` is refused.  Returns ``(form, T)``, ``T`` None with ``linear``."""
+    form = cfg.get("rank_loss_form", None)
+    if form is None:
+        form = "linear"
+    if not isinstance(form, str) or form not in RANK_LOSS_FORMS:
+        raise ValueError(f"rank_loss_form must be 'linear' or 'logistic', not {form!r}")
+    value = cfg.get("rank_temperature", None)
+    if form != "logistic":
+        if value is not None:
+            raise ValueError("rank_temperature: with rank_loss_form: logistic only")
+        return form, None
+    if value is None:
+        value = 1.0
+    # (the kernel works with the value as fp32: that, too, is finite and > 0)
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not (0.0 < float(value) < float("inf")) or \
+            not 0.0 < ctypes.c_float(float(value)).value < float("inf"):
+        raise ValueError(f"rank_temperature must be a finite number > 0, not {value!r}")
+    if world_size > 1 and str(cfg.get("rank_loss_pairs", "local")) == "global":
+        raise ValueError("rank_loss_form: logistic: rank_loss_pairs: local only")
+    return form, float(value)
+
+
 REPORT_WEIGHTS = {"final": "final.pt", "ema": "final_ema.pt"}
 
 

@@ -119,6 +119,11 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     # statistics are reset at every epoch boundary: the file carries nothing of them)
     if cfg.get("style_decorr") is not None:
         fp["cfg.style_decorr"] = float(cfg["style_decorr"])
+    # `rank_loss_form` / `rank_temperature` likewise, when set: another form or temperature is another phase-B gradient
+    if cfg.get("rank_loss_form") is not None:
+        fp["cfg.rank_loss_form"] = str(cfg["rank_loss_form"])
+    if cfg.get("rank_temperature") is not None:
+        fp["cfg.rank_temperature"] = float(cfg["rank_temperature"])
     # (`rank_metrics` stays out: it adds a file beside the run and shapes nothing of the training, so a run may be
     # resumed with the key turned on or off)
     spec = np.asarray(train_spec, dtype=np.float64)

@@ -26,6 +26,10 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
   ``style_decorr`` a number w > 0 (default absent: off): phase B of every training step minimises ``aux_loss + w * D``, ``D``
                 the mean squared off-diagonal Pearson correlation of the styles over the batch (its exact gradient is added
                 on the device); one ``messages.txt`` line per epoch with the epoch's mean ``D``; no logged loss changes
+  ``rank_loss_form`` ``linear`` (default) | ``logistic``: with ``logistic`` phase B of every training step minimises the
+                pairwise logistic loss ``T * softplus(-s * (z_i - z_j) / T)`` over the labelled pairs instead of the
+                reference's linear one (``rank_temperature: T``, default 1.0, in style standard deviations);
+                ``kendall_activation`` is not applied to it; ``Train_Aux`` is that loss, ``Val_Aux`` stays the linear one
 
 Data parallel (the north star's replacement of the ipyparallel trial farm): started under
 ``torch.distributed.run`` (WORLD_SIZE > 1) every rank builds the same ``Trainer``; rank r steps rows
@@ -47,7 +51,8 @@ from .dataloader import get_dataloaders
 from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
 from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, ema_decay_of,
-                        grad_clip_norm_of, rank_metrics_on, resume_on, spec_broaden_of, spec_shift_of, style_decorr_of)
+                        grad_clip_norm_of, rank_loss_form_of, rank_metrics_on, resume_on, spec_broaden_of, spec_shift_of,
+                        style_decorr_of)
 from . import resume as resume_file
 
 
@@ -144,6 +149,7 @@ class Trainer:
         self.detect_anomaly = detect_anomaly_on(cfg)
         self.rank_metrics = rank_metrics_on(cfg)
         self.style_decorr = style_decorr_of(cfg)
+        self.rank_loss_form, self.rank_temperature = rank_loss_form_of(cfg, self._world_size())
         # `checkpoint_every` / `resume` (rankaae_amd/resume.py): the trial's resume file at epoch boundaries.  Refused
         # where it cannot be checked: data parallel (per-rank generator state, the private communicator's lifetime) and
         # the parity mode (its random tape is drawn from the global CPU generator in the reference's order)
@@ -345,6 +351,12 @@ class Trainer:
         if lead and self.style_decorr is not None:
             self.logger.info(f"style_decorr: w = {self.style_decorr:g} (phase B minimises aux_loss + w * D, D the mean "
                              "squared off-diagonal correlation of the styles over the batch)")
+        if lead and self.rank_loss_form == "logistic":
+            self.logger.info(f"rank_loss_form: logistic, rank_temperature T = {self.rank_temperature:g} (phase B minimises "
+                             "T * softplus(-s * (z_i - z_j) / T) over the labelled pairs; Train_Aux is that loss, Val_Aux "
+                             "stays the linear rank loss)")
+            self.logger.info("rank_loss_form: logistic: kendall_activation is not applied to the training rank loss (the "
+                             "sigmoid is the pair weight)")
         if lead and self.rank_metrics:
             self.logger.info("rank_metrics: Kendall tau-b of every descriptor's style on the validation split, every epoch")
         best_chpt_file, metrics = None, None

@@ -73,6 +73,9 @@ class TrialBatch:
             if (e.style_decorr is None) != (e0.style_decorr is None):
                 # (the value may differ: every grid plane of raae_style_decorr_fwd_bwd reads its own weight)
                 raise ValueError("the engines of a TrialBatch must agree on whether style_decorr is set")
+            if getattr(e, "rank_loss_form", "linear") != getattr(e0, "rank_loss_form", "linear"):
+                # (the temperature may differ: every grid plane of raae_rank_logistic_fwd_bwd reads its own)
+                raise ValueError("the engines of a TrialBatch must agree on rank_loss_form")
             if e.rank_metrics != e0.rank_metrics:
                 raise ValueError("the engines of a TrialBatch must agree on rank_metrics")
             if not e.cfg.get("fused_step_begin", True) or not e.cfg.get("fused_discriminator", True):
