@@ -983,40 +983,6 @@ extern "C" long raae_rank_loss_work_bytes(int B, int n_aux) {
     return (long)rank_part_bytes() + 2L * RANK_MAXNJ * B * n_aux * (long)sizeof(float) + 64 * (long)sizeof(double) + 256;
 }
 
-static int rank_pairs_launch(const float* d, int ldd, const float* z, int ldz, int n_all, int row0, int nrows, int n_aux,
-                             void* work, RankGrid& g, float*& gpos, float*& gneg, hipStream_t st) {
-    g = rank_grid(n_all, nrows, n_aux);
-    RankWork* part = (RankWork*)work;
-    gpos = (float*)((char*)work + rank_part_bytes());
-    gneg = gpos + (size_t)RANK_MAXNJ * nrows * n_aux;
-    const RankPairsArgs pa = {d, ldd, z, ldz, n_all, row0, nrows, g.nj, g.jchunk, part, gpos, gneg};
-#define RANK_CASE(KA) case KA: \
-        if (g.R == 1) raae::launch(rank_pairs_kernel<KA, 1>, rank_pairs_kernel_m<KA, 1>, dim3(g.nwg), dim3(256), 0, st, pa); \
-        else raae::launch(rank_pairs_kernel<KA, 4>, rank_pairs_kernel_m<KA, 4>, dim3(g.nwg), dim3(256), 0, st, pa); \
-        break;
-    switch (n_aux) {
-        RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
-        RANK_CASE(9) RANK_CASE(10) RANK_CASE(11) RANK_CASE(12) RANK_CASE(13) RANK_CASE(14) RANK_CASE(15) RANK_CASE(16)
-        default: return RAAE_EINVAL;
-    }
-#undef RANK_CASE
-    return (int)hipGetLastError();
-}
-
-extern "C" int raae_rank_loss_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
-                                      void* work, float* loss, float* dz, void* stream) {
-    RAAE_CHECK_ARG(d && z && work && loss && B > 1 && n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
-    hipStream_t st = (hipStream_t)stream;
-    RankGrid g;
-    float *gpos, *gneg;
-    const int rc = rank_pairs_launch(d, ldd, z, ldz, B, 0, B, n_aux, work, g, gpos, gneg, st);
-    if (rc) return rc;
-    const int gf = dz ? grid_for((long)B * ldz, 256, 256) : 1;
-    const RankFinArgs fa = {(const RankWork*)work, g.nwg, (const double*)nullptr, B, B, g.nj, n_aux, activate, 1.f, gpos, gneg, loss, dz, ldz};
-    raae::launch(rank_finalize_kernel, rank_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
-    RAAE_LAUNCH_RET();
-}
-
 // The rank loss on a batch with unlabelled cells (a descriptor that is not finite): same pair pass, same grid, plus the
 // labelled-row counts [RANK_MAXWG][16] ints behind the gradient partials of the work buffer.
 static size_t rank_grad_bytes(int B, int n_aux) { return (2 * (size_t)RANK_MAXNJ * B * n_aux * sizeof(float) + 255) & ~(size_t)255; }
@@ -1024,40 +990,87 @@ extern "C" long raae_rank_loss_masked_work_bytes(int B, int n_aux) {
     return (long)(rank_part_bytes() + rank_grad_bytes(B, n_aux) + (size_t)RANK_MAXWG * RANK_MAXK * sizeof(int) + 256);
 }
 
-// the masked pair pass of rows [row0, row0 + nrows) against all n_all rows; the work buffer's layout follows nrows
-static int rank_pairs_masked_launch(const float* d, int ldd, const float* z, int ldz, int n_all, int row0, int nrows, int n_aux,
-                                    void* work, RankGrid& g, float*& gpos, float*& gneg, int*& labelled, hipStream_t st) {
-    g = rank_grid(n_all, nrows, n_aux);
-    gpos = (float*)((char*)work + rank_part_bytes());
-    gneg = gpos + (size_t)RANK_MAXNJ * nrows * n_aux;
-    labelled = (int*)((char*)work + rank_part_bytes() + rank_grad_bytes(nrows, n_aux));
-    const RankMaskedPairsArgs pa = {{d, ldd, z, ldz, n_all, row0, nrows, g.nj, g.jchunk, (RankWork*)work, gpos, gneg}, labelled};
-#define RANK_CASE(KA) case KA: \
-        if (g.R == 1) raae::launch(rank_pairs_masked_kernel<KA, 1>, rank_pairs_masked_kernel_m<KA, 1>, dim3(g.nwg), dim3(256), 0, st, pa); \
-        else raae::launch(rank_pairs_masked_kernel<KA, 4>, rank_pairs_masked_kernel_m<KA, 4>, dim3(g.nwg), dim3(256), 0, st, pa); \
+// The work buffer of every linear form: the workgroups' partials, the column blocks' g+ and g- of the nrows rows that
+// the pair pass owns, and (masked forms only: the unmasked buffer ends before them, so NULL there) the workgroups'
+// labelled-row counts.
+struct RankLayout { RankWork* part; float* gpos; float* gneg; int* labelled; };
+static RankLayout rank_layout(void* work, int nrows, int n_aux, bool masked) {
+    float* gpos = (float*)((char*)work + rank_part_bytes());
+    return {(RankWork*)work, gpos, gpos + (size_t)RANK_MAXNJ * nrows * n_aux,
+            masked ? (int*)((char*)work + rank_part_bytes() + rank_grad_bytes(nrows, n_aux)) : nullptr};
+}
+
+// RANK_DISPATCH launches KERNEL<n_aux, g.R> (with its batched twin KERNEL_m) over the pair grid g; for an n_aux outside
+// 1..16 it RETURNS RAAE_EINVAL from the function that uses it.
+#define RANK_CASE(KERNEL, KA, g, st, pa) case KA: \
+        if ((g).R == 1) raae::launch(KERNEL<KA, 1>, KERNEL##_m<KA, 1>, dim3((g).nwg), dim3(256), 0, st, pa); \
+        else raae::launch(KERNEL<KA, 4>, KERNEL##_m<KA, 4>, dim3((g).nwg), dim3(256), 0, st, pa); \
         break;
-    switch (n_aux) {
-        RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
-        RANK_CASE(9) RANK_CASE(10) RANK_CASE(11) RANK_CASE(12) RANK_CASE(13) RANK_CASE(14) RANK_CASE(15) RANK_CASE(16)
-        default: return RAAE_EINVAL;
+#define RANK_DISPATCH(KERNEL, n_aux, g, st, pa) switch (n_aux) { \
+        RANK_CASE(KERNEL, 1, g, st, pa) RANK_CASE(KERNEL, 2, g, st, pa) RANK_CASE(KERNEL, 3, g, st, pa) \
+        RANK_CASE(KERNEL, 4, g, st, pa) RANK_CASE(KERNEL, 5, g, st, pa) RANK_CASE(KERNEL, 6, g, st, pa) \
+        RANK_CASE(KERNEL, 7, g, st, pa) RANK_CASE(KERNEL, 8, g, st, pa) RANK_CASE(KERNEL, 9, g, st, pa) \
+        RANK_CASE(KERNEL, 10, g, st, pa) RANK_CASE(KERNEL, 11, g, st, pa) RANK_CASE(KERNEL, 12, g, st, pa) \
+        RANK_CASE(KERNEL, 13, g, st, pa) RANK_CASE(KERNEL, 14, g, st, pa) RANK_CASE(KERNEL, 15, g, st, pa) \
+        RANK_CASE(KERNEL, 16, g, st, pa) \
+        default: return RAAE_EINVAL; \
     }
-#undef RANK_CASE
-    return (int)hipGetLastError();
+
+// The pair pass of rows [row0, row0 + nrows) against all n_all rows (the work buffer's layout follows nrows) and, where
+// `totals` is given, this rank's totals: [5][16] doubles from the masked pass, [4][16] otherwise.
+static int rank_pairs_launch(const float* d, int ldd, const float* z, int ldz, int n_all, int row0, int nrows, int n_aux,
+                             bool masked, void* work, double* totals, hipStream_t st) {
+    const RankGrid g = rank_grid(n_all, nrows, n_aux);
+    const RankLayout w = rank_layout(work, nrows, n_aux, masked);
+    const RankMaskedPairsArgs pa = {{d, ldd, z, ldz, n_all, row0, nrows, g.nj, g.jchunk, w.part, w.gpos, w.gneg}, w.labelled};
+    if (masked) {
+        RANK_DISPATCH(rank_pairs_masked_kernel, n_aux, g, st, pa)
+    } else {
+        RANK_DISPATCH(rank_pairs_kernel, n_aux, g, st, pa.p)
+    }
+    const int rc = (int)hipGetLastError();
+    if (rc || !totals) return rc;
+    if (masked)
+        RAAE_PLAIN_LAUNCH(rank_masked_totals_kernel, dim3(1), dim3(256), 0, st, (const RankWork*)w.part, (const int*)w.labelled,
+                          g.nwg, n_aux, totals);
+    else
+        RAAE_PLAIN_LAUNCH(rank_totals_kernel, dim3(1), dim3(256), 0, st, (const RankWork*)w.part, g.nwg, n_aux, totals);
+    RAAE_LAUNCH_RET();
+}
+
+// The finalize over the nrows rows of a pair pass: from the pass's own partials (`totals` NULL: the whole batch,
+// nrows == n_all) or from totals that the caller has summed over the ranks.  The three finalize kernels stay apart: one
+// kernel for all forms measured 1 us slower per launch at 4096 rows.
+static int rank_finish_launch(const double* totals, bool masked, int n_all, int nrows, int n_aux, int activate, float scale,
+                              void* work, float* loss, float* dz, int ldz, hipStream_t st) {
+    const RankGrid g = rank_grid(n_all, nrows, n_aux);
+    const RankLayout w = rank_layout(work, nrows, n_aux, masked);
+    const int gf = dz ? grid_for((long)nrows * ldz, 256, 256) : 1;
+    if (!masked) {
+        const RankFinArgs fa = {w.part, g.nwg, totals, n_all, nrows, g.nj, n_aux, activate, scale, w.gpos, w.gneg, loss, dz, ldz};
+        raae::launch(rank_finalize_kernel, rank_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
+    } else if (totals) {
+        const RankRowsMaskedFinArgs fa = {totals, nrows, g.nj, n_aux, activate, scale, w.gpos, w.gneg, loss, dz, ldz};
+        raae::launch(rank_rows_masked_finalize_kernel, rank_rows_masked_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
+    } else {
+        const RankMaskedFinArgs fa = {w.part, w.labelled, g.nwg, nrows, g.nj, n_aux, activate, w.gpos, w.gneg, loss, dz, ldz};
+        raae::launch(rank_masked_finalize_kernel, rank_masked_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
+    }
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_rank_loss_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
+                                      void* work, float* loss, float* dz, void* stream) {
+    RAAE_CHECK_ARG(d && z && work && loss && B > 1 && n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
+    const int rc = rank_pairs_launch(d, ldd, z, ldz, B, 0, B, n_aux, false, work, nullptr, (hipStream_t)stream);
+    return rc ? rc : rank_finish_launch(nullptr, false, B, B, n_aux, activate, 1.f, work, loss, dz, ldz, (hipStream_t)stream);
 }
 
 extern "C" int raae_rank_loss_masked_fwd_bwd(const float* d, int ldd, const float* z, int ldz, int B, int n_aux, int activate,
                                              void* work, float* loss, float* dz, void* stream) {
     RAAE_CHECK_ARG(d && z && work && loss && B > 1 && n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
-    hipStream_t st = (hipStream_t)stream;
-    RankGrid g;
-    float *gpos, *gneg;
-    int* labelled;
-    const int rc = rank_pairs_masked_launch(d, ldd, z, ldz, B, 0, B, n_aux, work, g, gpos, gneg, labelled, st);
-    if (rc) return rc;
-    const int gf = dz ? grid_for((long)B * ldz, 256, 256) : 1;
-    const RankMaskedFinArgs fa = {(const RankWork*)work, labelled, g.nwg, B, g.nj, n_aux, activate, gpos, gneg, loss, dz, ldz};
-    raae::launch(rank_masked_finalize_kernel, rank_masked_finalize_kernel_m, dim3(gf), dim3(256), 0, st, fa);
-    RAAE_LAUNCH_RET();
+    const int rc = rank_pairs_launch(d, ldd, z, ldz, B, 0, B, n_aux, true, work, nullptr, (hipStream_t)stream);
+    return rc ? rc : rank_finish_launch(nullptr, true, B, B, n_aux, activate, 1.f, work, loss, dz, ldz, (hipStream_t)stream);
 }
 
 // The logistic rank loss: work = loss partials [RANK_MAXWG][16] doubles, labelled-row counts [RANK_MAXWG][16] ints, the
@@ -1082,22 +1095,15 @@ extern "C" int raae_rank_logistic_fwd_bwd(const float* d, int ldd, const float* 
     int* lab = (int*)((char*)work + rank_logistic_lossp_bytes());
     float* gpart = (float*)((char*)work + rank_logistic_lossp_bytes() + rank_logistic_lab_bytes());
     const RankLogArgs pa = {d, ldd, z, ldz, B, g.nj, g.jchunk, T, lossp, lab, gpart};
-#define RANK_CASE(KA) case KA: \
-        if (g.R == 1) raae::launch(rank_logistic_kernel<KA, 1>, rank_logistic_kernel_m<KA, 1>, dim3(g.nwg), dim3(256), 0, st, pa); \
-        else raae::launch(rank_logistic_kernel<KA, 4>, rank_logistic_kernel_m<KA, 4>, dim3(g.nwg), dim3(256), 0, st, pa); \
-        break;
-    switch (n_aux) {
-        RANK_CASE(1) RANK_CASE(2) RANK_CASE(3) RANK_CASE(4) RANK_CASE(5) RANK_CASE(6) RANK_CASE(7) RANK_CASE(8)
-        RANK_CASE(9) RANK_CASE(10) RANK_CASE(11) RANK_CASE(12) RANK_CASE(13) RANK_CASE(14) RANK_CASE(15) RANK_CASE(16)
-        default: return RAAE_EINVAL;
-    }
-#undef RANK_CASE
+    RANK_DISPATCH(rank_logistic_kernel, n_aux, g, st, pa)
     const int rc = (int)hipGetLastError();
     if (rc) return rc;
     const RankLogFinArgs fa = {lossp, lab, g.nwg, B, g.nj, n_aux, T, gpart, loss, dz, lddz};
     raae::launch(rank_logistic_finish_kernel, rank_logistic_finish_kernel_m, dim3(grid_for((long)B * lddz, 256, 256)), dim3(256), 0, st, fa);
     RAAE_LAUNCH_RET();
 }
+#undef RANK_DISPATCH
+#undef RANK_CASE
 
 // One rank's share of the GLOBAL pairs of a data-parallel batch (rows [row0, row0 + nrows) against all n_all rows):
 // pair pass + this rank's totals; after the caller has summed `totals` over the ranks, raae_rank_rows_finish forms
@@ -1106,26 +1112,14 @@ extern "C" int raae_rank_rows_pairs(const float* d_all, int ldd, const float* z_
                                     int n_aux, void* work, double* totals, void* stream) {
     RAAE_CHECK_ARG(d_all && z_all && work && totals && n_all > 1 && nrows >= 1 && row0 >= 0 && row0 + nrows <= n_all &&
                    n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
-    hipStream_t st = (hipStream_t)stream;
-    RankGrid g;
-    float *gpos, *gneg;
-    const int rc = rank_pairs_launch(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, work, g, gpos, gneg, st);
-    if (rc) return rc;
-    RAAE_PLAIN_LAUNCH(rank_totals_kernel, dim3(1), dim3(256), 0, st, (const RankWork*)work, g.nwg, n_aux, totals);
-    RAAE_LAUNCH_RET();
+    return rank_pairs_launch(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, false, work, totals, (hipStream_t)stream);
 }
 
 extern "C" int raae_rank_rows_finish(const double* totals, int n_all, int nrows, int n_aux, int activate, float scale,
                                      void* work, float* loss, float* dz, int ldz, void* stream) {
     RAAE_CHECK_ARG(totals && work && loss && n_all > 1 && nrows >= 1 && nrows <= n_all && n_aux >= 1 && n_aux <= RANK_MAXK &&
                    (!dz || ldz >= n_aux));
-    const RankGrid g = rank_grid(n_all, nrows, n_aux);
-    float* gpos = (float*)((char*)work + rank_part_bytes());
-    float* gneg = gpos + (size_t)RANK_MAXNJ * nrows * n_aux;
-    const int gf = dz ? grid_for((long)nrows * ldz, 256, 256) : 1;
-    const RankFinArgs fa = {(const RankWork*)nullptr, 0, totals, n_all, nrows, g.nj, n_aux, activate, scale, gpos, gneg, loss, dz, ldz};
-    raae::launch(rank_finalize_kernel, rank_finalize_kernel_m, dim3(gf), dim3(256), 0, (hipStream_t)stream, fa);
-    RAAE_LAUNCH_RET();
+    return rank_finish_launch(totals, false, n_all, nrows, n_aux, activate, scale, work, loss, dz, ldz, (hipStream_t)stream);
 }
 
 // The rows-against-all pair on a batch with missing labels: the masked pair pass over this rank's rows, its totals with
@@ -1137,29 +1131,14 @@ extern "C" int raae_rank_rows_masked_pairs(const float* d_all, int ldd, const fl
                                            int nrows, int n_aux, void* work, double* totals, void* stream) {
     RAAE_CHECK_ARG(d_all && z_all && work && totals && n_all > 1 && nrows >= 1 && row0 >= 0 && row0 + nrows <= n_all &&
                    n_aux >= 1 && n_aux <= RANK_MAXK && ldd >= n_aux && ldz >= n_aux);
-    hipStream_t st = (hipStream_t)stream;
-    RankGrid g;
-    float *gpos, *gneg;
-    int* labelled;
-    const int rc = rank_pairs_masked_launch(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, work, g, gpos, gneg, labelled, st);
-    if (rc) return rc;
-    RAAE_PLAIN_LAUNCH(rank_masked_totals_kernel, dim3(1), dim3(256), 0, st, (const RankWork*)work, (const int*)labelled, g.nwg,
-                      n_aux, totals);
-    RAAE_LAUNCH_RET();
+    return rank_pairs_launch(d_all, ldd, z_all, ldz, n_all, row0, nrows, n_aux, true, work, totals, (hipStream_t)stream);
 }
 
 extern "C" int raae_rank_rows_masked_finish(const double* totals, int n_all, int nrows, int n_aux, int activate, float scale,
                                             void* work, float* loss, float* dz, int ldz, void* stream) {
     RAAE_CHECK_ARG(totals && work && loss && n_all > 1 && nrows >= 1 && nrows <= n_all && n_aux >= 1 && n_aux <= RANK_MAXK &&
                    (!dz || ldz >= n_aux));
-    const RankGrid g = rank_grid(n_all, nrows, n_aux);
-    float* gpos = (float*)((char*)work + rank_part_bytes());
-    float* gneg = gpos + (size_t)RANK_MAXNJ * nrows * n_aux;
-    const int gf = dz ? grid_for((long)nrows * ldz, 256, 256) : 1;
-    const RankRowsMaskedFinArgs fa = {totals, nrows, g.nj, n_aux, activate, scale, gpos, gneg, loss, dz, ldz};
-    raae::launch(rank_rows_masked_finalize_kernel, rank_rows_masked_finalize_kernel_m, dim3(gf), dim3(256), 0,
-                 (hipStream_t)stream, fa);
-    RAAE_LAUNCH_RET();
+    return rank_finish_launch(totals, true, n_all, nrows, n_aux, activate, scale, work, loss, dz, ldz, (hipStream_t)stream);
 }
 
 extern "C" int raae_recon_loss_fwd_bwd(const float* spec_in, const float* spec_out, int B, int L, int scale,

@@ -1063,12 +1063,9 @@ class StepEngine:
 
     def _rank_loss(self, P, styles):
         """Phase B's loss and d(loss)/d(styles).  Data parallel with ``rank_loss_pairs: global``: the ranks exchange
-        their [b, n_aux] descriptors and styles (all-gather), every rank pairs ITS rows with all W*b rows, the
-        per-descriptor pair counts and sums meet in one 512-byte all-reduce, and the row-local gradient is exact;
-        it is scaled by W because the parameter gradients are averaged over the ranks afterwards.  Missing labels
-        (``aux_missing``): the masked kernels; with global pairs the all-reduce also carries the per-descriptor
-        labelled-row counts (640 bytes), so every rank normalises by the labelled pairs of the whole batch."""
-        c, b, ns, lo = self.cfg, P.b, self.nstyle, self.loss_out
+        their [b, n_aux] descriptors and styles (all-gather) and every rank pairs ITS rows with all W*b rows; the
+        row-local gradient is exact and is scaled by W because the parameter gradients are averaged over the ranks."""
+        b, ns, lo = P.b, self.nstyle, self.loss_out
         if self.rank_loss_form == "logistic":
             # `rank_loss_form: logistic`: one kernel for labelled and partly labelled data, over this rank's own rows
             # (global pairs are refused at construction); `kendall_activation` does not apply, the sigmoid is the weight
@@ -1076,18 +1073,32 @@ class StepEngine:
                                       lo[1:2], P.dstyles, ns)
             return
         if not self.rank_pairs_global:
-            # (missing labels: rows without a label for descriptor k leave its pairs)
-            fwd_bwd = ops.rank_loss_masked_fwd_bwd if self.aux_missing else ops.rank_loss_fwd_bwd
-            fwd_bwd(P.aux, self.n_aux, styles, ns, b, self.n_aux, c["kendall_activation"], P.rank_work, lo[1:2], P.dstyles)
+            self._linear_rank_loss(P.aux, styles, b, 0, b, P.rank_work, None, lo[1:2], P.dstyles, 1.0)
             return
         W = self.world_size
-        pairs, finish = ((ops.rank_rows_masked_pairs, ops.rank_rows_masked_finish) if self.aux_missing else
-                         (ops.rank_rows_pairs, ops.rank_rows_finish))
         self._collective(P.aux, "gather", P.aux_all)
         self._collective(styles, "gather", P.z_all)
-        pairs(P.aux_all, self.n_aux, P.z_all, ns, W * b, self.rank * b, b, self.n_aux, P.rank_work, P.rank_totals)
-        self._collective(P.rank_totals, "sum")
-        finish(P.rank_totals, W * b, b, self.n_aux, c["kendall_activation"], float(W), P.rank_work, lo[1:2], P.dstyles, ns)
+        self._linear_rank_loss(P.aux_all, P.z_all, W * b, self.rank * b, b, P.rank_work, P.rank_totals, lo[1:2], P.dstyles,
+                               float(W))
+
+    def _linear_rank_loss(self, aux, z, n_all, row0, nrows, work, totals, loss, dz, scale):
+        """The linear rank loss of rows [row0, row0 + nrows) against all n_all rows of ``aux`` / ``z``; missing labels
+        (``aux_missing``): the masked kernels.  ``totals`` None: the whole batch in one entry point.  Otherwise one
+        rank's share: the pair pass, the per-descriptor pair counts and sums (masked: and labelled-row counts, so every
+        rank normalises by the labelled pairs of the whole batch) summed over the ranks in one 512- or 640-byte
+        all-reduce, and the finish, whose ``dz`` is multiplied by ``scale``.  A rank with nrows == 0 (``totals`` zeroed
+        by its caller) skips only the pair pass."""
+        ns, ka, act = self.nstyle, self.n_aux, self.cfg["kendall_activation"]
+        if totals is None:
+            fwd_bwd = ops.rank_loss_masked_fwd_bwd if self.aux_missing else ops.rank_loss_fwd_bwd
+            fwd_bwd(aux, ka, z, ns, n_all, ka, act, work, loss, dz)
+            return
+        pairs, finish = ((ops.rank_rows_masked_pairs, ops.rank_rows_masked_finish) if self.aux_missing else
+                         (ops.rank_rows_pairs, ops.rank_rows_finish))
+        if nrows > 0:
+            pairs(aux, ka, z, ns, n_all, row0, nrows, ka, work, totals)
+        self._collective(totals, "sum")
+        finish(totals, n_all, max(nrows, 1), ka, act, scale, work, loss, dz, ns)
 
     def _begin_phase(self, record):
         self._slab_notes = np.zeros(self.arena.n // 64, dtype=np.int16) if record else None
@@ -1648,9 +1659,8 @@ class StepEngine:
         # n_val rows (raae_rank_rows_pairs), the per-descriptor counts and sums meet in one 512-byte float64 all-reduce,
         # and raae_rank_rows_finish forms the loss, identical on every rank and equal to the replicated computation to
         # the order of the float64 sums (47 ms -> 47 / W ms at n_val = 150 k).  The O(n_val) parts (forwards, the four
-        # other losses, the style metrics, which need every row's styles) stay replicated.
-        # Missing labels: the same split by the masked pair (raae_rank_rows_masked_pairs / _finish), whose all-reduce
-        # also carries the labelled-row counts per descriptor (640 bytes): n_val^2 / W pairs per rank instead of n_val^2.
+        # other losses, the style metrics, which need every row's styles) stay replicated.  Missing labels: the same
+        # split by the masked pair (`_linear_rank_loss`): n_val^2 / W pairs per rank instead of n_val^2.
         shard = self.world_size > 1 and bool(c.get("shard_validation", True))
         per = (nv + self.world_size - 1) // self.world_size          # rows per rank of the sharded pair pass
         if key not in self.plans:
@@ -1693,23 +1703,13 @@ class StepEngine:
             out = self.dec.forward(V.dec, z, None, train=False)
             ops.recon_loss_fwd_bwd(val_spec, out, nv, self.L, False, V.lpart, None, fin=(1.0, V.out, 2, -1, V.ticket))
             if shard:
-                pairs, finish = ((ops.rank_rows_masked_pairs, ops.rank_rows_masked_finish) if self.aux_missing else
-                                 (ops.rank_rows_pairs, ops.rank_rows_finish))
                 row0 = min(self.rank * per, nv)
                 nrows = min(per, nv - row0)
-                if nrows > 0:
-                    pairs(val_aux, self.n_aux, z, ns, nv, row0, nrows, self.n_aux, V.rank_work, V.rank_totals)
-                else:                       # more ranks than validation rows: this rank adds nothing
+                if nrows == 0:              # more ranks than validation rows: this rank adds nothing
                     V.rank_totals.zero_()
-                self._collective(V.rank_totals, "sum")
-                finish(V.rank_totals, nv, max(nrows, 1), self.n_aux, c["kendall_activation"], 1.0, V.rank_work,
-                       V.out[1:2], None, ns)
-            elif self.aux_missing:
-                ops.rank_loss_masked_fwd_bwd(val_aux, self.n_aux, z, ns, nv, self.n_aux, c["kendall_activation"],
-                                             V.rank_work, V.out[1:2], None)
+                self._linear_rank_loss(val_aux, z, nv, row0, nrows, V.rank_work, V.rank_totals, V.out[1:2], None, 1.0)
             else:
-                ops.rank_loss_fwd_bwd(val_aux, self.n_aux, z, ns, nv, self.n_aux, c["kendall_activation"], V.rank_work,
-                                      V.out[1:2], None)
+                self._linear_rank_loss(val_aux, z, nv, 0, nv, V.rank_work, None, V.out[1:2], None, 1.0)
             ops.smooth_loss_fwd_bwd(out, nv, self.L, self.taps, V.lpart, None, fin=(1.0, V.out, 4, -1, V.ticket))
             z_s = V.tape.view(V.z_sample, nv, ns)
             out2 = self.dec.forward(V.dec, z_s, None, train=False)

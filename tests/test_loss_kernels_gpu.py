@@ -527,6 +527,28 @@ def test_rank_rows(name):
     rep.done()
 
 
+@pytest.mark.parametrize("B", [33, 1027])
+def test_rank_rows_single_split_is_the_whole_batch(B):
+    """One rank that owns every row: ``raae_rank_rows_pairs`` + ``raae_rank_rows_finish`` (scale 1) and
+    ``raae_rank_loss_fwd_bwd`` run one pair pass, one reduction of its records, one set of coefficients and one dz loop,
+    and the counts pass through the totals exactly, so loss and dz have the same bits.  33 rows: one column block and
+    fewer than 16 records; 1027 rows: R = 4, several column blocks, more than 16 records (the slice loop takes more than
+    one trip)."""
+    K = 5
+    d, z = rank_data(f"one_{B}", B, K, False, False)
+    form = lr.rank_form(B, B, K, False)
+    assert (form["nwg"] > 16, form["nj"] > 1, form["R"]) == ((True, True, 4) if B == 1027 else (False, False, 1)), form
+    whole, rows = RankDev(d, z, K, False), RankDev(d, z, K, False, B)
+    for act in (False, True):
+        whole.whole(act)
+        rows.pairs(0)
+        rows.finish(rows.totals.t, act, 1.0)
+        torch.cuda.synchronize()
+        assert torch.equal(_bits(whole.loss.t), _bits(rows.loss.t)), f"activate={act}: loss bits differ"
+        assert torch.equal(_bits(whole.dz.t), _bits(rows.dz.t)), f"activate={act}: dz bits differ"
+        assert all(b.guard_ok() for b in (rows.totals, rows.loss, rows.dz, rows.work))
+
+
 # ============================================================================================ recon, smooth, MSE, BCE
 def _loss_of(part, n, scale=1.0):
     out = torch.zeros(8, device=DEV)

@@ -133,6 +133,9 @@ def test_one_rank_is_the_single_gpu_masked_kernel(name, act):
     ops.rank_loss_masked_fwd_bwd(ranks.d, K, ranks.z, ld, B, K, act, work, loss, dz)
     torch.cuda.synchronize()
     print(f"{name} activate={act}: loss bitwise {torch.equal(loss, ranks.loss[0])}, dz bitwise {torch.equal(dz, ranks.dz[0])}")
+    # one finalize kernel forms both from the same reduction, coefficients and dz loop, and the counts pass through the
+    # totals exactly: the same bits
+    assert torch.equal(loss, ranks.loss[0]) and torch.equal(dz, ranks.dz[0])
     _loss_close(float(ranks.loss[0]), float(loss), f"{name} W=1 against rank_loss_masked_fwd_bwd")
     _close(ranks.stacked_dz(), dz.cpu().double().numpy(), f"{name} W=1 dz")
 
