@@ -746,11 +746,40 @@ int raae_spec_augment(const float* spec, const long* idx, const int* cursor, con
 int raae_spec_augment2(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
                        int B, int L, double max_sigma, double max_shift, double spec_noise, long noise_goff,
                        float* spec_out, void* stream);
+/* ---- normalisation augmentation of the training batch (ABI 33; config keys `spec_gain`, `spec_tilt`) ----
+ * raae_spec_augment3: raae_spec_augment2 with a per-row gain and a per-row linear tilt between the shift and the noise
+ * (resolution, axis, normalisation, detector).  Called BEHIND raae_step_begin on the same state and writes, out of place,
+ *     spec_out[b][l] = g_b * x + c_b * r_l + z * spec_noise,   x = shift(broaden(spec[idx[cursor - B + b]], sigma_b), l + delta_b)
+ * The new stage ("Normalisation augmentation"), every line one fp32 operation, compiled with
+ * contraction off:
+ *   draws    u_b  = float(lowbias32(lowbias32(b + 0xA0000000 + k1) ^ k2) >> 8) * 2^-24   (exact)
+ *            u'_b = float(lowbias32(lowbias32(b + 0xE0000000 + k1) ^ k2) >> 8) * 2^-24   (exact)
+ *            with B <= 2^29 neither range meets the dropout elements (< 2^31), the shift draws (0x80000000 + b), the
+ *            broaden draws (0xC0000000 + b) or the other
+ *   gain     g_b = 1 + (2 u_b - 1) * a,  a = (float)max_gain: 2 u - 1 exact, the product rounds, the sum rounds;
+ *            g_b in [1 - a, 1 + a)
+ *   tilt     c_b = (2 u'_b - 1) * t,  t = (float)max_tilt: the product rounds;  |c_b| <= t
+ *   ramp     r_l = float(2 l - (L - 1)) / float(L - 1): the integer is exact, the correctly rounded division rounds;
+ *            from -1 at l = 0 to +1 at l = L - 1;  L == 1: r = 0
+ *   row      v = g_b * x;  p = c_b * r_l;  v = v + p: three roundings
+ * Broadening, shift and noise are raae_spec_augment2's own functions and expressions, the Gaussian numbering included:
+ * with max_gain == 0 and max_tilt == 0 the output is raae_spec_augment2's up to the sign of a zero (1 * x = x, x + (+-0)).
+ * max_sigma == 0 skips the broadening, max_shift == 0 shifts by nothing, spec_noise == 0 adds nothing.  g_b and c_b
+ * depend on the seed, the counter and b alone.  Geometry and LDS image are raae_spec_augment2's; no atomics, fixed
+ * order: the result does not depend on the grid and a graph replay is bitwise the eager call.  spec and spec_out must
+ * not overlap.
+ *   1 <= B <= 2^29, 1 <= L <= 8192, no NULL pointer, max_shift finite and >= 0, max_sigma finite, >= 0 and
+ *   ceil(3 s) <= 64 (as floats), 0 <= (float)max_gain < 1, max_tilt >= 0 and finite as a float, spec_noise not NaN,
+ *   noise_goff >= 0 (any alignment).  Anything else: RAAE_EINVAL, nothing is launched and nothing written.
+ * Has the batched form: plane z reads its own argument block, so the trials of a batch may differ in all four values. */
+int raae_spec_augment3(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
+                       int B, int L, double max_sigma, double max_shift, double max_gain, double max_tilt,
+                       double spec_noise, long noise_goff, float* spec_out, void* stream);
 
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
- * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2, since ABI 30 raae_kendall_tau, since ABI 31 raae_style_decorr_fwd_bwd, since ABI 32 raae_rank_logistic_fwd_bwd) and of the conv networks' fused
+ * raae_disc_fused, raae_rank_loss_fwd_bwd, the three loss kernels, raae_adam_step, raae_optim_step(_chk / _clip), raae_grad_norm, since ABI 26 raae_slab_reduce, raae_ema_step, raae_spec_augment and raae_spec_augment2, since ABI 30 raae_kendall_tau, since ABI 31 raae_style_decorr_fwd_bwd, since ABI 32 raae_rank_logistic_fwd_bwd, since ABI 33 raae_spec_augment3) and of the conv networks' fused
  * path (raae_block_fwd_a / _b / _a2 / _b2, raae_block_bwd_b / _a / _b_wgrad, raae_block_wgrad, the decoder head -- their
  * large-batch instances included, ABI 17) exist in a second form whose grid plane z works on trial z's argument block;
  * the per-layer conv entry points (raae_conv_*, raae_lenlin_*, raae_sum3_fwd, raae_grad_materialize) do not.  raae_record_begin/end log the launches one trial makes on the calling
@@ -795,7 +824,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 32
+#define RAAE_ABI_VERSION 33
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

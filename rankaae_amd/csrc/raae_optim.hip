@@ -839,6 +839,110 @@ __global__ __launch_bounds__(256) void spec_augment2_kernel_m(const SpecAug2Args
     spec_augment2_body(a);
 }
 
+// ---- normalisation augmentation (config keys `spec_gain`, `spec_tilt`): row b scaled by g_b and tilted by a linear
+// ramp c_b r_l, between the shift and the noise ----
+// The kernel above with one more stage: resolution, axis, NORMALISATION, detector.  Its own body (the two kernels above
+// stay what they are, bit for bit), the same geometry: one workgroup per row, the row in LDS, stages 1 and 2 as above.
+// Row b draws two more uniforms from the step's hash, u_b at index SPEC_GAIN_OFF + b and u'_b at SPEC_TILT_OFF + b;
+// with B <= 2^29 the four ranges 0x80000000 (shift), 0xA0000000 (gain), 0xC0000000 (broaden), 0xE0000000 (tilt) + b
+// are disjoint from one another and from the dropout elements (< 2^31), the last one ending at 2^32 - 1.
+//   g_b = 1 + (2 u_b - 1) a      2 u - 1 exact; the product rounds; the sum rounds
+//   c_b = (2 u'_b - 1) t         the product rounds
+//   r_l = float(2 l - (L - 1)) / float(L - 1)     the integer is exact (|.| < 2^13); the division rounds; L == 1: r = 0
+//   v   = g_b x;  p = c_b r_l;  v = v + p          three roundings, x the shifted sample
+// all compiled with contraction off (a product fused into the sum would skip its rounding), so a fp32 emulation on the
+// host reproduces the stage bit for bit.  a == 0 gives g_b = 1 and v = x, t == 0 gives p = +-0 and v + p = v (up to
+// the sign of a zero): no case is skipped, there is one body.  g_b, c_b are one value per row, computed by every
+// thread from the hash (two scalars: nothing to stage, no barrier); r_l is computed where it is used.  Stage 3 keeps
+// the quad-per-thread layout of the kernel above: the noise comes in Philox blocks of four consecutive elements, so a
+// lane reads LDS words 4 t + k (32-bit reads at a stride of four words: four lanes share a bank, which a row of a few
+// hundred samples does not feel; a lane-consecutive layout would draw every Philox block four times).  The noise term
+// is the kernel's above, in the same (default) contraction context, so it is formed by the same instructions.
+constexpr uint32_t SPEC_GAIN_OFF = 0xA0000000u;
+constexpr uint32_t SPEC_TILT_OFF = 0xE0000000u;
+constexpr int SPEC_NORM_BMAX = 1 << 29;
+struct SpecAug3Args {
+    const float* spec; const long* idx; const int* cursor; const unsigned long long* rng_state; int B; int L;
+    float max_sigma; float max_shift; float max_gain; float max_tilt; float spec_noise; long noise_goff; float* spec_out;
+};
+// (2 u - 1) * m for the draw at hash index b + off: spec_shift_delta's expression at another index
+__device__ __forceinline__ float spec_norm_draw(uint32_t b, uint32_t off, uint32_t k1, uint32_t k2, float m) {
+#pragma clang fp contract(off)
+    const uint32_t h = raae::lowbias32(raae::lowbias32(b + off + k1) ^ k2);
+    const float u = (float)(h >> 8) * (1.0f / 16777216.0f);       // exact: 24 bits
+    return (2.f * u - 1.f) * m;                                   // (2 u - 1 is exact; the product is the only rounding)
+}
+__device__ __forceinline__ float spec_norm_gain(uint32_t b, uint32_t k1, uint32_t k2, float a) {
+#pragma clang fp contract(off)
+    const float d = spec_norm_draw(b, SPEC_GAIN_OFF, k1, k2, a);
+    return 1.f + d;                                               // rounds
+}
+__device__ __forceinline__ float spec_norm_ramp(int l, int L) {
+#pragma clang fp contract(off)
+    return L == 1 ? 0.f : (float)(2 * l - (L - 1)) / (float)(L - 1);      // (the correctly rounded division rounds)
+}
+__device__ __forceinline__ float spec_norm_apply(float x, float g, float c, float r) {
+#pragma clang fp contract(off)
+    const float v = g * x, p = c * r;                             // each rounds
+    return v + p;                                                 // rounds
+}
+__device__ __forceinline__ void spec_augment3_body(const SpecAug3Args& a) {
+    extern __shared__ float s_aug3[];
+    const int L = a.L, R = spec_broaden_radius(a.max_sigma), tid = threadIdx.x;
+    float* s_in = s_aug3;                                         // L + 2 R of the L + 2 RMAX
+    float* s_w = s_aug3 + L + 2 * SPEC_BROADEN_RMAX;              // 2 R + 1 of the 2 RMAX + 4
+    float* s_g = s_w + 2 * SPEC_BROADEN_RMAX + 4;                 // L
+    const unsigned long long ctr = a.rng_state[0], seed = a.rng_state[1];
+    const uint32_t k1 = reinterpret_cast<const unsigned*>(a.rng_state + 2)[0];
+    const uint32_t k2 = reinterpret_cast<const unsigned*>(a.rng_state + 2)[1];
+    const long* idx = a.idx + (a.cursor[0] - a.B);
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        const float* row = a.spec + (size_t)idx[b] * L;
+        const float sigma = spec_broaden_sigma((uint32_t)b, k1, k2, a.max_sigma);
+        if (sigma == 0.f) {                                       // (the whole workgroup agrees: one row, one sigma)
+            for (int l = tid; l < L; l += 256) s_g[l] = row[l];
+        } else {
+            for (int i = tid; i < L + 2 * R; i += 256) s_in[i] = row[min(max(i - R, 0), L - 1)];
+            if (tid <= 2 * R) s_w[tid] = spec_broaden_weight(tid - R, spec_broaden_q(sigma));
+            __syncthreads();
+            for (int l = tid; l < L; l += 256) {
+                float acc = 0.f, wsum = 0.f;
+                for (int j = 0; j <= 2 * R; ++j) {
+                    const float w = s_w[j];
+                    wsum += w;
+                    acc = fmaf(w, s_in[l + j], acc);
+                }
+                s_g[l] = acc / wsum;
+            }
+        }
+        __syncthreads();
+        const float delta = spec_shift_delta((uint32_t)b, k1, k2, a.max_shift);
+        const float gain = spec_norm_gain((uint32_t)b, k1, k2, a.max_gain);
+        const float tilt = spec_norm_draw((uint32_t)b, SPEC_TILT_OFF, k1, k2, a.max_tilt);
+        const long e0 = a.noise_goff + (long)b * L;               // the row's first element in the Gaussian numbering
+        float* out = a.spec_out + (size_t)b * L;
+        for (long q4 = (e0 >> 2) + tid; q4 * 4 < e0 + L; q4 += 256) {
+            float z[4] = {0.f, 0.f, 0.f, 0.f};
+            if (a.spec_noise != 0.f) normal4(q4, ctr, seed, z);
+            const long l0 = q4 * 4 - e0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const long l = l0 + k;
+                if (l < 0 || l >= L) continue;
+                float v = spec_norm_apply(spec_shift_sample(s_g, (int)l, L, delta), gain, tilt, spec_norm_ramp((int)l, L));
+                if (a.spec_noise != 0.f) v += z[k] * a.spec_noise;
+                out[l] = v;
+            }
+        }
+        __syncthreads();                                          // (the next row overwrites the LDS image)
+    }
+}
+__global__ __launch_bounds__(256) void spec_augment3_kernel(SpecAug3Args a) { spec_augment3_body(a); }
+__global__ __launch_bounds__(256) void spec_augment3_kernel_m(const SpecAug3Args* t) {
+    const SpecAug3Args a = t[blockIdx.z];
+    spec_augment3_body(a);
+}
+
 }  // namespace
 
 extern "C" int raae_adam_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
@@ -1018,6 +1122,32 @@ extern "C" int raae_spec_augment2(const float* spec, const long* idx, const int*
     }();
     if (lds_limit != hipSuccess) return (int)lds_limit;
     raae::launch(spec_augment2_kernel, spec_augment2_kernel_m, dim3(B < 1024 ? B : 1024), dim3(256), lds, (hipStream_t)stream, a);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_spec_augment3(const float* spec, const long* idx, const int* cursor, const unsigned long long* rng_state,
+                                  int B, int L, double max_sigma, double max_shift, double max_gain, double max_tilt,
+                                  double spec_noise, long noise_goff, float* spec_out, void* stream) {
+    // (B <= 2^29: the gain draws at 0xA0000000 + b end below the broaden draws, the tilt draws at 0xE0000000 + b below 2^32)
+    RAAE_CHECK_ARG(spec && idx && cursor && rng_state && spec_out && B >= 1 && B <= SPEC_NORM_BMAX && L >= 1 && L <= SPEC_BROADEN_LMAX);
+    const float sg = (float)max_sigma, s = (float)max_shift, gn = (float)max_gain, tl = (float)max_tilt, sn = (float)spec_noise;
+    RAAE_CHECK_ARG(max_shift >= 0.0 && s < INFINITY && sn == sn);      // (false for a NaN or Inf max_shift)
+    RAAE_CHECK_ARG(max_sigma >= 0.0 && sg < INFINITY);                 // (likewise)
+    RAAE_CHECK_ARG(spec_broaden_radius_ok(sg));                        // (a float comparison: 1e10 or 3e38 is refused here)
+    RAAE_CHECK_ARG(max_gain >= 0.0 && gn < 1.f);                       // (as the kernel sees it: 1 - 1e-12 rounds to 1; false for a NaN)
+    RAAE_CHECK_ARG(max_tilt >= 0.0 && tl < INFINITY);                  // (false for a NaN or Inf, and for a finite double beyond fp32)
+    RAAE_CHECK_ARG(noise_goff >= 0);                                   // (any alignment: the body takes whole quads of the numbering)
+    const SpecAug3Args a = {spec, idx, cursor, rng_state, B, L, sg, s, gn, tl, sn, noise_goff, spec_out};
+    // raae_spec_augment2's geometry and LDS image, and its word to the runtime about more than 64 KiB
+    const size_t lds = sizeof(float) * (size_t)(2 * L + 4 * SPEC_BROADEN_RMAX + 4);
+    static const hipError_t lds_limit = [] {
+        const int most = (int)(sizeof(float) * (2 * SPEC_BROADEN_LMAX + 4 * SPEC_BROADEN_RMAX + 4));
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(spec_augment3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(spec_augment3_kernel_m), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        return e;
+    }();
+    if (lds_limit != hipSuccess) return (int)lds_limit;
+    raae::launch(spec_augment3_kernel, spec_augment3_kernel_m, dim3(B < 1024 ? B : 1024), dim3(256), lds, (hipStream_t)stream, a);
     RAAE_LAUNCH_RET();
 }
 

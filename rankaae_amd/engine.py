@@ -27,7 +27,7 @@ from . import _lib, ops, schedule
 from .metrics import KendallTau, StyleMetrics
 from .schedule import Pass
 from .parameter import (check_optimizer, detect_anomaly_on, ema_decay_of, grad_clip_norm_of, rank_loss_form_of,
-                        rank_metrics_on, spec_broaden_of, spec_shift_of, style_decorr_of)
+                        rank_metrics_on, spec_broaden_of, spec_gain_of, spec_shift_of, spec_tilt_of, style_decorr_of)
 from ._lib import (IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP, OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS,
                    OUT_RELU, G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU, RAAE_MAX_PARTS)
 
@@ -477,6 +477,11 @@ class StepEngine:
         # build-only key `spec_broaden` (default absent: off), checked likewise: every training step convolves the rows
         # of its batch with a Gaussian of a random per-row width, in front of the shift, in that one launch (`emit_step`)
         self.spec_broaden = spec_broaden_of(cfg, rng_mode)
+        # build-only keys `spec_gain`, `spec_tilt` (default absent: off), checked likewise: every training step scales
+        # the rows of its batch by a random per-row factor and tilts them by a random per-row ramp, behind the shift,
+        # in that one launch (`emit_step`)
+        self.spec_gain = spec_gain_of(cfg, rng_mode)
+        self.spec_tilt = spec_tilt_of(cfg, rng_mode)
         # build-only key `rank_metrics` (default false), checked likewise: every validation also forms Kendall's tau-b of
         # each descriptor against its style, two launches behind the style metrics (`validate`)
         self.rank_metrics = rank_metrics_on(cfg)
@@ -898,6 +903,10 @@ class StepEngine:
         if self.spec_broaden is not None:
             # the width of row b is drawn at SPEC_BROADEN_OFF + b: beyond every dropout element and every shift draw
             assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF and b < 2 ** 30
+        if self.spec_gain is not None or self.spec_tilt is not None:
+            # the gain and the tilt of row b are drawn at SPEC_GAIN_OFF + b and SPEC_TILT_OFF + b: with b < 2^29 beyond
+            # every dropout element and between, or beyond, the shift and the broaden draws
+            assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF and b <= ops.SPEC_NORM_BMAX
         P.rank_work = torch.empty(self._rank_work_bytes(b, rows_form=self.rank_pairs_global, train=True), dtype=torch.uint8,
                                   device=dev)
         if self.rank_pairs_global:
@@ -1143,7 +1152,17 @@ class StepEngine:
         if P.stride is None:
             P.stride = stride
         assert P.stride == stride, "cursor stride is baked into the captured graph of this batch size"
-        if self.spec_broaden is not None:
+        if self.spec_gain is not None or self.spec_tilt is not None:
+            # `spec_gain` / `spec_tilt` (with or without `spec_broaden` and `spec_shift`): the head as below, and ONE
+            # launch behind it that broadens the rows, shifts them, scales and tilts them (each by nothing where its
+            # key is absent) and adds the noise
+            ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,
+                           self.train_spec, self.train_aux, self.perm, b, self.L, self.n_aux, 0.0, None, -P.noise - 1,
+                           P.spec, P.aux, tape)
+            ops.spec_augment3(self.train_spec, self.perm, self.cursor, self.rng_state, b, self.L, self.spec_broaden or 0.0,
+                              self.spec_shift or 0.0, self.spec_gain or 0.0, self.spec_tilt or 0.0,
+                              float(c["spec_noise"]), -P.noise - 1, P.spec)
+        elif self.spec_broaden is not None:
             # `spec_broaden` (with or without `spec_shift`): the head as below, and ONE launch behind it that broadens
             # the rows, shifts them (by nothing without `spec_shift`) and adds the noise
             ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,

@@ -480,6 +480,23 @@ def spec_augment2(spec, idx, cursor, rng_state, B, L, max_sigma, max_shift, spec
                                          int(noise_goff), _ptr(spec_out), _stream()), "raae_spec_augment2")
 
 
+SPEC_GAIN_OFF = 0xA0000000      # hash index of row 0's gain draw: between the shift draws and the broaden draws (b < 2^29)
+SPEC_TILT_OFF = 0xE0000000      # hash index of row 0's tilt draw: beyond every broaden draw; ends at 2^32 - 1 (b < 2^29)
+SPEC_NORM_BMAX = 2 ** 29        # the most rows raae_spec_augment3 takes: above it the four ranges of draws would meet
+
+
+def spec_augment3(spec, idx, cursor, rng_state, B, L, max_sigma, max_shift, max_gain, max_tilt, spec_noise, noise_goff,
+                  spec_out):
+    """``raae_spec_augment3`` (config keys ``spec_gain``, ``spec_tilt``): ``spec_augment2`` with row b, behind its
+    broadening and its shift and before the noise, multiplied by ``g_b = 1 + (2 u_b - 1) max_gain`` and tilted by
+    ``c_b r_l``, ``c_b = (2 u'_b - 1) max_tilt``, ``r_l = (2 l - (L - 1)) / (L - 1)``; both draws from the step's hash
+    keys.  One launch, ``spec_augment2``'s geometry; any of the four values may be 0."""
+    assert rng_state.dtype == torch.int64 and rng_state.numel() >= 3 and cursor.dtype == torch.int32
+    check(_lib.load().raae_spec_augment3(_ptr(spec), _ptr(idx, torch.int64), _ptr(cursor, torch.int32), _ptr(rng_state, torch.int64),
+                                         int(B), int(L), float(max_sigma), float(max_shift), float(max_gain), float(max_tilt),
+                                         float(spec_noise), int(noise_goff), _ptr(spec_out), _stream()), "raae_spec_augment3")
+
+
 def slab_reduce(g_slabs, slab_stride, seg_nslab, n, out, max_nslab=512):
     check(_lib.load().raae_slab_reduce(_ptr(g_slabs), slab_stride, _ptr(seg_nslab, torch.int16), n, _ptr(out),
                                        int(max_nslab), _stream()), "raae_slab_reduce")

@@ -110,6 +110,58 @@ def spec_broaden_of(cfg, rng_mode=None):
     return float(value)
 
 
+def _fp32_of(value):
+    """``value`` as the kernel sees it, rounded to fp32 (Inf for a finite number beyond fp32), or None for anything that
+    is not a real number (a bool, a string, an integer beyond every float)."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)):
+        return None
+    try:
+        return ctypes.c_float(float(value)).value
+    except OverflowError:
+        return None
+
+
+def _step_head_rng(cfg, rng_mode):
+    return (rng_mode if rng_mode is not None else cfg.get("rng_mode", "philox")) == "philox" and \
+        bool(cfg.get("fused_step_begin", True))
+
+
+def spec_gain_of(cfg, rng_mode=None):
+    """Build-only key ``spec_gain`` (default absent / ``null``: off): a finite float ``a`` with ``0 < a < 1``, the
+    largest relative error of the normalisation.  Every training step then multiplies row b of its batch by
+    ``g_b = 1 + (2 u_b - 1) a``, ``u_b`` uniform in ``[0, 1)`` and drawn per row on the device, behind the broadening
+    and the energy shift and before the spectral noise; validation and every export see the rows as they are.  The
+    bounds hold for the value as the kernel sees it, in fp32 (``1 - 1e-12`` rounds to 1 and is refused).  Needs
+    ``rng_mode: philox`` and ``fused_step_begin``, like ``spec_shift``.  Returns the float, or None."""
+    value = cfg.get("spec_gain", None)
+    if value is None:
+        return None
+    f = _fp32_of(value)
+    if f is None or not (0.0 < float(value) and f < 1.0):
+        raise ValueError(f"spec_gain must be absent, null or a finite number a with 0 < a < 1, not {value!r}")
+    if not _step_head_rng(cfg, rng_mode):
+        raise ValueError("spec_gain: device RNG with the fused step head only")
+    return float(value)
+
+
+def spec_tilt_of(cfg, rng_mode=None):
+    """Build-only key ``spec_tilt`` (default absent / ``null``: off): a finite float ``t > 0``, the largest height of a
+    residual linear background at the ends of a row.  Every training step then adds ``c_b r_l`` to row b of its batch,
+    ``c_b = (2 u'_b - 1) t`` drawn per row on the device and ``r_l`` running from -1 at the first sample to +1 at the
+    last, behind the gain (``spec_gain``) and before the spectral noise; validation and every export see the rows as
+    they are.  Finite means finite in fp32, as the kernel sees it.  Needs ``rng_mode: philox`` and
+    ``fused_step_begin``, like ``spec_shift``.  Returns the float, or None."""
+    value = cfg.get("spec_tilt", None)
+    if value is None:
+        return None
+    f = _fp32_of(value)
+    if f is None or not (0.0 < float(value) and f < float("inf")):
+        raise ValueError(f"spec_tilt must be absent, null or a finite number > 0, not {value!r}")
+    if not _step_head_rng(cfg, rng_mode):
+        raise ValueError("spec_tilt: device RNG with the fused step head only")
+    return float(value)
+
+
 def style_decorr_of(cfg):
     """Build-only key ``style_decorr`` (default absent / ``null``: off): a finite float ``w > 0``, the weight of the
     decorrelation penalty.  Phase B of every training step then minimises ``aux_loss + w * D``, ``D`` the mean squared

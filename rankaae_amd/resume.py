@@ -115,6 +115,10 @@ def fingerprint(cfg, tile_mult, arena_n, n_train, n_val, train_spec):
     # `spec_broaden` likewise
     if cfg.get("spec_broaden") is not None:
         fp["cfg.spec_broaden"] = float(cfg["spec_broaden"])
+    # `spec_gain` and `spec_tilt` likewise
+    for key in ("spec_gain", "spec_tilt"):
+        if cfg.get(key) is not None:
+            fp["cfg." + key] = float(cfg[key])
     # `style_decorr` likewise: a run with another weight would continue on another phase-B gradient (its per-epoch
     # statistics are reset at every epoch boundary: the file carries nothing of them)
     if cfg.get("style_decorr") is not None:

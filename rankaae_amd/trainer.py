@@ -20,6 +20,12 @@ Build-only config keys (all optional, defaults preserve reference behaviour):
   ``spec_broaden`` a number s > 0 with ceil(3 s) <= 64 (default absent: off): every training step convolves each row of its
                 batch with a Gaussian of a random width of up to s grid points, on the device, before the shift and the
                 spectral noise; validation never broadens
+  ``spec_gain`` a number a with 0 < a < 1 (default absent: off): every training step multiplies each row of its batch by a
+                random factor in [1 - a, 1 + a), on the device, behind the shift and before the spectral noise (an edge
+                step normalised a few per cent wrong); validation never scales
+  ``spec_tilt`` a number t > 0 (default absent: off): every training step adds to each row of its batch a linear ramp of a
+                random height of up to t at the ends (-c at the first sample, +c at the last, |c| <= t), on the device,
+                behind the gain and before the spectral noise (a background not quite removed); validation never tilts
   ``rank_metrics`` true | false (default): every epoch's validation also forms Kendall's tau-b of each descriptor against
                 its style on the device, over the validation rows labelled for it, and rank 0 appends one row to
                 ``rank_metrics.csv`` (``Epoch,Tau_*,Labelled_*``); nothing else a run writes or returns changes
@@ -51,8 +57,8 @@ from .dataloader import get_dataloaders
 from .engine import OPT_NAMES, StepEngine
 from .model import AE_CLS_DICT, DiscriminatorFC
 from .parameter import (Parameters, check_optimizer, checkpoint_every_of, detect_anomaly_on, ema_decay_of,
-                        grad_clip_norm_of, rank_loss_form_of, rank_metrics_on, resume_on, spec_broaden_of, spec_shift_of,
-                        style_decorr_of)
+                        grad_clip_norm_of, rank_loss_form_of, rank_metrics_on, resume_on, spec_broaden_of, spec_gain_of,
+                        spec_shift_of, spec_tilt_of, style_decorr_of)
 from . import resume as resume_file
 
 
@@ -146,6 +152,8 @@ class Trainer:
         self.ema_decay = ema_decay_of(cfg)
         self.spec_shift = spec_shift_of(cfg)
         self.spec_broaden = spec_broaden_of(cfg)
+        self.spec_gain = spec_gain_of(cfg)
+        self.spec_tilt = spec_tilt_of(cfg)
         self.detect_anomaly = detect_anomaly_on(cfg)
         self.rank_metrics = rank_metrics_on(cfg)
         self.style_decorr = style_decorr_of(cfg)
@@ -348,6 +356,10 @@ class Trainer:
             self.logger.info(f"spec_shift: rows shifted by up to ±{self.spec_shift:g} grid points")
         if lead and self.spec_broaden is not None:
             self.logger.info(f"spec_broaden: rows broadened by a Gaussian of up to σ = {self.spec_broaden:g} grid points")
+        if lead and self.spec_gain is not None:
+            self.logger.info(f"spec_gain: rows scaled by a factor in [1 − {self.spec_gain:g}, 1 + {self.spec_gain:g})")
+        if lead and self.spec_tilt is not None:
+            self.logger.info(f"spec_tilt: rows tilted by a ramp of up to ±{self.spec_tilt:g} at the ends")
         if lead and self.style_decorr is not None:
             self.logger.info(f"style_decorr: w = {self.style_decorr:g} (phase B minimises aux_loss + w * D, D the mean "
                              "squared off-diagonal correlation of the styles over the batch)")

@@ -70,6 +70,10 @@ class TrialBatch:
             if (e.spec_broaden is None) != (e0.spec_broaden is None):
                 # (the value may differ: every grid plane of raae_spec_augment2 reads its own largest sigma)
                 raise ValueError("the engines of a TrialBatch must agree on whether spec_broaden is set")
+            for key in ("spec_gain", "spec_tilt"):
+                # (the values may differ: every grid plane of raae_spec_augment3 reads its own)
+                if (getattr(e, key, None) is None) != (getattr(e0, key, None) is None):
+                    raise ValueError(f"the engines of a TrialBatch must agree on whether {key} is set")
             if (e.style_decorr is None) != (e0.style_decorr is None):
                 # (the value may differ: every grid plane of raae_style_decorr_fwd_bwd reads its own weight)
                 raise ValueError("the engines of a TrialBatch must agree on whether style_decorr is set")
