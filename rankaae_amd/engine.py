@@ -897,16 +897,13 @@ class StepEngine:
         P.m_enc.append(self.enc.mask_slots(tape, b))            # phase E :191
         P.m_dec.append(self.dec.mask_slots(tape, b))
         tape.finalize(dev)
-        if self.spec_shift is not None:
-            # the shift of row b is drawn at hash index SPEC_SHIFT_OFF + b: beyond every dropout element of the step
+        norm = self.spec_gain is not None or self.spec_tilt is not None
+        if norm or self.spec_broaden is not None or self.spec_shift is not None:
+            # row b draws at hash indices SPEC_SHIFT_OFF + b (shift), SPEC_BROADEN_OFF + b (width), SPEC_GAIN_OFF + b
+            # and SPEC_TILT_OFF + b: beyond every dropout element of the step, and apart from one another with b < 2^30
+            # (shift and width) or b <= 2^29 (all four)
             assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF
-        if self.spec_broaden is not None:
-            # the width of row b is drawn at SPEC_BROADEN_OFF + b: beyond every dropout element and every shift draw
-            assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF and b < 2 ** 30
-        if self.spec_gain is not None or self.spec_tilt is not None:
-            # the gain and the tilt of row b are drawn at SPEC_GAIN_OFF + b and SPEC_TILT_OFF + b: with b < 2^29 beyond
-            # every dropout element and between, or beyond, the shift and the broaden draws
-            assert tape.total <= ops.SPEC_SHIFT_OFF and tape.htotal <= ops.SPEC_SHIFT_OFF and b <= ops.SPEC_NORM_BMAX
+            assert b <= ops.SPEC_NORM_BMAX if norm else (self.spec_broaden is None or b < 2 ** 30)
         P.rank_work = torch.empty(self._rank_work_bytes(b, rows_form=self.rank_pairs_global, train=True), dtype=torch.uint8,
                                   device=dev)
         if self.rank_pairs_global:
@@ -1152,33 +1149,24 @@ class StepEngine:
         if P.stride is None:
             P.stride = stride
         assert P.stride == stride, "cursor stride is baked into the captured graph of this batch size"
-        if self.spec_gain is not None or self.spec_tilt is not None:
-            # `spec_gain` / `spec_tilt` (with or without `spec_broaden` and `spec_shift`): the head as below, and ONE
-            # launch behind it that broadens the rows, shifts them, scales and tilts them (each by nothing where its
-            # key is absent) and adds the noise
+        norm = self.spec_gain is not None or self.spec_tilt is not None
+        if norm or self.spec_broaden is not None or self.spec_shift is not None:
+            # an augmentation key: the head ticks, fills the tape, gathers `aux` and writes the rows as they are (no
+            # noise); ONE launch behind it overwrites `P.spec` with the rows broadened, shifted, scaled and tilted (each
+            # by nothing where its key is absent), plus the noise -- every phase of the step reads that one augmented
+            # batch.  The kernel is the one that has the stages of the keys that are set and no more.
             ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,
                            self.train_spec, self.train_aux, self.perm, b, self.L, self.n_aux, 0.0, None, -P.noise - 1,
                            P.spec, P.aux, tape)
-            ops.spec_augment3(self.train_spec, self.perm, self.cursor, self.rng_state, b, self.L, self.spec_broaden or 0.0,
-                              self.spec_shift or 0.0, self.spec_gain or 0.0, self.spec_tilt or 0.0,
-                              float(c["spec_noise"]), -P.noise - 1, P.spec)
-        elif self.spec_broaden is not None:
-            # `spec_broaden` (with or without `spec_shift`): the head as below, and ONE launch behind it that broadens
-            # the rows, shifts them (by nothing without `spec_shift`) and adds the noise
-            ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,
-                           self.train_spec, self.train_aux, self.perm, b, self.L, self.n_aux, 0.0, None, -P.noise - 1,
-                           P.spec, P.aux, tape)
-            ops.spec_augment2(self.train_spec, self.perm, self.cursor, self.rng_state, b, self.L, self.spec_broaden,
-                              self.spec_shift or 0.0, float(c["spec_noise"]), -P.noise - 1, P.spec)
-        elif self.spec_shift is not None:
-            # `spec_shift`: the head ticks, fills the tape, gathers `aux` and writes the rows as they are (no noise);
-            # the launch behind it overwrites `P.spec` with the rows resampled at their shifts, plus the noise -- every
-            # phase of the step reads that one augmented batch
-            ops.step_begin(self.steps_dev, 5, mask_bits, self.rng_state, self.cursor, stride, self.begin_ticket,
-                           self.train_spec, self.train_aux, self.perm, b, self.L, self.n_aux, 0.0, None, -P.noise - 1,
-                           P.spec, P.aux, tape)
-            ops.spec_augment(self.train_spec, self.perm, self.cursor, self.rng_state, b, self.L, self.spec_shift,
-                             float(c["spec_noise"]), -P.noise - 1, P.spec)
+            src = (self.train_spec, self.perm, self.cursor, self.rng_state, b, self.L)
+            dst = (float(c["spec_noise"]), -P.noise - 1, P.spec)
+            if norm:
+                ops.spec_augment3(*src, self.spec_broaden or 0.0, self.spec_shift or 0.0, self.spec_gain or 0.0,
+                                  self.spec_tilt or 0.0, *dst)
+            elif self.spec_broaden is not None:
+                ops.spec_augment2(*src, self.spec_broaden, self.spec_shift or 0.0, *dst)
+            else:
+                ops.spec_augment(*src, self.spec_shift, *dst)
         elif self.fused_begin:
             # tick + tape fill + gather in ONE launch (was three: 19 us of the 256-row step)
             philox = self.rng_mode == "philox"

@@ -33,13 +33,23 @@ def step_keys(seed, counter):
     return np.uint32(k1), np.uint32(k2)
 
 
-def uniforms(n_rows, seed, counter):
-    """``u_b`` of rows ``0 .. n_rows - 1``, fp32, in ``[0, 1)`` (24 bits: exact)."""
+def row_hashes(n_rows, seed, counter, off):
+    """``lowbias32(lowbias32(b + off + k1) ^ k2)`` of rows ``0 .. n_rows - 1``: the 32-bit stream at index range ``off``
+    (every per-row draw of the augmentation kernels: shift, width, gain, tilt)."""
     k1, k2 = step_keys(seed, counter)
     with np.errstate(over="ignore"):
-        b = np.arange(n_rows, dtype=np.uint32) + np.uint32(OFF) + k1
-    h = lowbias32(lowbias32(b) ^ k2)
-    return (h >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+        b = np.arange(n_rows, dtype=np.uint32) + np.uint32(off) + k1
+    return lowbias32(lowbias32(b) ^ k2)
+
+
+def row_uniforms(n_rows, seed, counter, off):
+    """``float(h_b >> 8) * 2^-24`` of that stream, fp32, in ``[0, 1)`` (24 bits: exact)."""
+    return (row_hashes(n_rows, seed, counter, off) >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+
+
+def uniforms(n_rows, seed, counter):
+    """``u_b`` of rows ``0 .. n_rows - 1``: the shift's draw."""
+    return row_uniforms(n_rows, seed, counter, OFF)
 
 
 def deltas(n_rows, seed, counter, s):

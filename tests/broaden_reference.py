@@ -8,7 +8,6 @@ is compared against differs from it by the kernel's own fp32 roundings only (``e
 import numpy as np
 
 import augment_reference as ar
-from augment_reference import lowbias32, step_keys
 
 OFF = 0xC0000000        # hash index of row 0's width draw: beyond every dropout element and every shift draw of a step
 RMAX = 64
@@ -22,11 +21,7 @@ def radius(s):
 
 def unit_draws(n_rows, seed, counter):
     """``v_b`` of rows ``0 .. n_rows - 1``, fp32, in ``[0, 1)`` (24 bits: exact)."""
-    k1, k2 = step_keys(seed, counter)
-    with np.errstate(over="ignore"):
-        b = np.arange(n_rows, dtype=np.uint32) + np.uint32(OFF) + k1
-    g = lowbias32(lowbias32(b) ^ k2)
-    return (g >> np.uint32(8)).astype(np.float32) * np.float32(2.0 ** -24)
+    return ar.row_uniforms(n_rows, seed, counter, OFF)
 
 
 def sigmas(n_rows, seed, counter, s):

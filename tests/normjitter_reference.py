@@ -11,26 +11,13 @@ Two forms of the one stage ``v = g_b x + c_b r_l``:
 * ``stage64``: the same stage in float64 from the exact 24-bit uniforms, no fp32 rounding anywhere."""
 import numpy as np
 
-from augment_reference import lowbias32, step_keys
+from augment_reference import row_hashes as hashes, row_uniforms as uniforms      # (at index range ``off``)
 
 GAIN_OFF = 0xA0000000       # hash index of row 0's gain draw
 TILT_OFF = 0xE0000000       # hash index of row 0's tilt draw
 BMAX = 2 ** 29              # the most rows the entry point takes
 U = 2.0 ** -24              # unit roundoff of fp32
 _F = np.float32
-
-
-def hashes(n_rows, seed, counter, off):
-    """``lowbias32(lowbias32(b + off + k1) ^ k2)`` of rows ``0 .. n_rows - 1``: the 32-bit stream at index range ``off``."""
-    k1, k2 = step_keys(seed, counter)
-    with np.errstate(over="ignore"):
-        b = np.arange(n_rows, dtype=np.uint32) + np.uint32(off) + k1
-    return lowbias32(lowbias32(b) ^ k2)
-
-
-def uniforms(n_rows, seed, counter, off):
-    """``u_b = float(h_b >> 8) * 2^-24``, fp32, in ``[0, 1)`` (24 bits: exact)."""
-    return (hashes(n_rows, seed, counter, off) >> np.uint32(8)).astype(_F) * _F(2.0 ** -24)
 
 
 def _signed(n_rows, seed, counter, off):
