@@ -1009,7 +1009,7 @@ static int prep_block_wgrad(const raae_block_wgrad_t* in, int* nslab, WgradMulti
 // that run it, so it computes what its own kernel computes.  X / Y are tags over the existing bodies.  The two are
 // independent, so they overlap on the chip like parallel graph branches would -- without the fork/join edges, which
 // at 256-row batches cost as much as the kernels.  co_pair below lists every instance.
-#include "raae_adam_body.inc"
+#include "raae_optim_body.inc"
 #define COMMA ,
 template <int K> struct CoFwdA {
     typedef BlockFwdAArgs Args;
@@ -1027,12 +1027,10 @@ template <int K> struct CoBwdB {
     typedef BlockBwdBArgs Args;
     static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float* dyn) { block_bwd_b_body<K>(a, bx, gx, dyn); }
 };
-template <bool CHK> struct CoAdam {             // adam_wide_kernel / adam_wide_chk_kernel (raae_optim.hip)
-    typedef AdamChkArgs Args;
-    static __device__ __forceinline__ void body(const Args& c, int bx, int gx, float*) {
-        const AdamArgs& a = c.a;
-        adam_wide_body<CHK>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
-                            c.nan_step, bx, gx);
+template <bool CHK> struct CoAdam {             // update_kernel<RAAE_OPT_ADAM, true, CHK, false> (raae_optim.hip)
+    typedef UpdateArgs Args;
+    static __device__ __forceinline__ void body(const Args& a, int bx, int gx, float*) {
+        update_body<RAAE_OPT_ADAM, true, CHK, false>(a, bx, gx);
     }
 };
 template <int KW> struct CoWgrad {               // wgrad_multi_kernel<KW>: all weight-gradient tasks of a block
@@ -1100,7 +1098,7 @@ struct CoSide {
     size_t lds = 0;
     bool big = false, large = false, chk = false, wide = false;
     int max_nslab = 0;
-    BlockFwdAArgs fa; BlockFwdBArgs fb; BlockBwdAArgs ba; BlockBwdBArgs bb; BwdBWgradArgs bw; AdamChkArgs ad; WgradMultiArgs wg;
+    BlockFwdAArgs fa; BlockFwdBArgs fb; BlockBwdAArgs ba; BlockBwdBArgs bb; BwdBWgradArgs bw; UpdateArgs ad; WgradMultiArgs wg;
     HeadFwdArgs hf;
     raae_co_conv_fwd_t cf;
 };
@@ -1145,15 +1143,15 @@ static int co_prep(int kind, const void* args, int* nparts, CoSide& s) {
         const raae_co_adam_t* p = (const raae_co_adam_t*)args;
         RAAE_CHECK_ARG(p->p && p->m && p->v && p->g_slabs && p->seg_nslab && p->hyper && p->step && p->n > 0 &&
                        (p->n % 64) == 0 && p->max_nslab >= 0 && (p->rule == RAAE_OPT_ADAM || p->rule == RAAE_OPT_ADAMW));
-        s.ad.a.p = p->p; s.ad.a.m = p->m; s.ad.a.v = p->v; s.ad.a.g_slabs = p->g_slabs; s.ad.a.slab_stride = p->slab_stride;
-        s.ad.a.seg_nslab = p->seg_nslab; s.ad.a.n = p->n; s.ad.a.hyper = p->hyper; s.ad.a.step = p->step;
-        s.ad.a.decoupled = p->rule == RAAE_OPT_ADAMW;
-        s.ad.a.gscale = nullptr;               // (a clipped update never rides: it follows its norm launch)
+        s.ad.p = p->p; s.ad.m = p->m; s.ad.v = p->v; s.ad.g_slabs = p->g_slabs; s.ad.slab_stride = p->slab_stride;
+        s.ad.seg_nslab = p->seg_nslab; s.ad.n = p->n; s.ad.hyper = p->hyper; s.ad.step = p->step;
+        s.ad.decoupled = p->rule == RAAE_OPT_ADAMW;
+        s.ad.gscale = nullptr;                 // (a clipped update never rides: it follows its norm launch)
         s.ad.nan_step = p->nan_step;
         s.chk = p->nan_step != nullptr;
         s.wide = p->max_nslab > 16;
         s.max_nslab = p->max_nslab;
-        long g = (p->n + 31) / 32;              // adam_wide_kernel's geometry (raae_adam_step)
+        long g = (p->n + 31) / 32;              // the wide update kernel's geometry (optim_grid, raae_optim.hip)
         if (g > 4096) g = 4096;
         s.grid = (int)g; s.lds = 0;
         return 0;
@@ -1210,12 +1208,10 @@ static int co_single(const CoSide& s, hipStream_t stream) {
         return raae_conv_fwd(s.cf.in, s.cf.B, s.cf.cv, s.cf.w, s.cf.bias, s.cf.out, RAAE_OUT_RAW, nullptr, nullptr, nullptr,
                              s.cf.act, stream);
     default: {
-        const AdamArgs& a = s.ad.a;
-        if (s.chk) return raae_optim_step_chk(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n,
-                                              a.decoupled ? RAAE_OPT_ADAMW : RAAE_OPT_ADAM, a.hyper, a.step, s.max_nslab,
-                                              s.ad.nan_step, stream);
-        return raae_adam_step(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
-                              s.max_nslab, stream);
+        const UpdateArgs& a = s.ad;            // (nan_step != NULL: raae_optim_step_chk's launch, else raae_optim_step's)
+        return raae_optim_step_clip(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n,
+                                    a.decoupled ? RAAE_OPT_ADAMW : RAAE_OPT_ADAM, a.hyper, a.step, s.max_nslab, a.nan_step,
+                                    nullptr, stream);
     }
     }
     RAAE_LAUNCH_RET();

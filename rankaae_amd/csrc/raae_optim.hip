@@ -7,348 +7,36 @@
 
 namespace {
 
-#include "raae_adam_body.inc"
+#include "raae_optim_body.inc"
 
+// ---- the update kernels: every rule x {one thread per element, WIDE} x {plain, CHK} x {no scale, SC} ----
+// (update_body: raae_optim_body.inc)
+template <int RULE, bool WIDE, bool CHK, bool SC>
+__global__ __launch_bounds__(256) void update_kernel(UpdateArgs a) { update_body<RULE, WIDE, CHK, SC>(a, blockIdx.x, gridDim.x); }
+template <int RULE, bool WIDE, bool CHK, bool SC>
+__global__ __launch_bounds__(256) void update_kernel_m(const UpdateArgs* t) {
+    const UpdateArgs a = t[blockIdx.z];
+    update_body<RULE, WIDE, CHK, SC>(a, blockIdx.x, gridDim.x);
+}
+// the instance of [rule][WIDE][CHK][SC]; Adam and AdamW share a family (UpdateArgs::decoupled)
+struct UpdateInst { void (*single)(UpdateArgs); void (*multi)(const UpdateArgs*); };
+#define RAAE_UPD(R, W, C, S) {update_kernel<R, W, C, S>, update_kernel_m<R, W, C, S>}
+#define RAAE_UPD_SHAPE(R, W) {{RAAE_UPD(R, W, false, false), RAAE_UPD(R, W, false, true)},                            \
+                              {RAAE_UPD(R, W, true, false), RAAE_UPD(R, W, true, true)}}
+#define RAAE_UPD_RULE(R) {RAAE_UPD_SHAPE(R, false), RAAE_UPD_SHAPE(R, true)}
+const UpdateInst kUpdate[4][2][2][2] = {RAAE_UPD_RULE(RAAE_OPT_ADAM), RAAE_UPD_RULE(RAAE_OPT_ADAM),
+                                        RAAE_UPD_RULE(RAAE_OPT_RADAM), RAAE_UPD_RULE(RAAE_OPT_ADABOUND)};
+#undef RAAE_UPD_RULE
+#undef RAAE_UPD_SHAPE
+#undef RAAE_UPD
 
-template <bool CHK, bool SC = false>
-__device__ __forceinline__ void adam_body(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
-                                          const unsigned short* seg_nslab, long n, const double* hyper,
-                                          const int* step, int decoupled, int* nan_step, const float* gscale = nullptr) {
-    __shared__ float s_sc[8];
-    if (threadIdx.x == 0) {
-        const double lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4];
-        const double t = (double)step[0];
-        const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
-        s_sc[0] = (float)(1.0 - lr * wd);      // AdamW decay factor
-        s_sc[1] = (float)(1.0 - b1);           // lerp weight
-        s_sc[2] = (float)b2;
-        s_sc[3] = (float)(1.0 - b2);
-        s_sc[4] = (float)(-(lr / bc1));        // -step_size
-        s_sc[5] = (float)sqrt(bc2);
-        s_sc[6] = (float)eps;
-        s_sc[7] = (float)wd;
-    }
-    __syncthreads();
-    const float decay = s_sc[0], w1 = s_sc[1], b2f = s_sc[2], omb2 = s_sc[3], nstep = s_sc[4], bc2s = s_sc[5],
-                epsf = s_sc[6], wdf = s_sc[7];
-    bool seen = false;
-    float gs = 1.f;
-    if (SC) gs = gscale[0];                 // the clip scale raae_grad_norm left (scale_grad: raae_adam_body.inc)
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int ns = seg_nslab[i >> 6];
-        if (ns == 0) continue;
-        // fixed-order slab sum, 8 independent loads in flight at a time
-        float g = 0.f;
-        int s = 0;
-        for (; s + 8 <= ns; s += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = g_slabs[(size_t)(s + u) * slab_stride + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) g += t[u];
-        }
-        for (; s < ns; ++s) g += g_slabs[(size_t)s * slab_stride + i];
-        if (CHK) seen |= __builtin_isnan(g);
-        if (SC) g = scale_grad(g, gs);
-        float pv = p[i];
-        if (decoupled) pv = pv * decay; else if (wdf != 0.f) g = g + wdf * pv;
-        float mv = m[i], vv = v[i];
-        mv = mv + w1 * (g - mv);
-        vv = vv * b2f;
-        vv = vv + (omb2 * g) * g;
-        const float denom = sqrtf(vv) / bc2s + epsf;
-        pv = pv + (nstep * mv) / denom;
-        p[i] = pv; m[i] = mv; v[i] = vv;
-    }
-    if (CHK) nan_vote(seen, nan_step, step);
-}
-
-__global__ __launch_bounds__(256) void adam_kernel(AdamArgs a) {
-    adam_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr);
-}
-__global__ __launch_bounds__(256) void adam_kernel_m(const AdamArgs* t) {
-    const AdamArgs a = t[blockIdx.z];
-    adam_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr);
-}
-// checked twins (AdamChkArgs: the argument block of the unchecked kernel + the flag word)
-__global__ __launch_bounds__(256) void adam_chk_kernel(AdamChkArgs c) {
-    const AdamArgs& a = c.a;
-    adam_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, c.nan_step);
-}
-__global__ __launch_bounds__(256) void adam_chk_kernel_m(const AdamChkArgs* t) {
-    const AdamChkArgs c = t[blockIdx.z];
-    const AdamArgs& a = c.a;
-    adam_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, c.nan_step);
-}
-
-// (adam_wide_body, the same update with the slabs of an element spread over 8 lanes: raae_adam_body.inc)
-__global__ __launch_bounds__(256) void adam_wide_kernel(AdamArgs a) {
-    adam_wide_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr, blockIdx.x, gridDim.x);
-}
-__global__ __launch_bounds__(256) void adam_wide_kernel_m(const AdamArgs* t) {
-    const AdamArgs a = t[blockIdx.z];
-    adam_wide_body<false>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled, nullptr, blockIdx.x, gridDim.x);
-}
-__global__ __launch_bounds__(256) void adam_wide_chk_kernel(AdamChkArgs c) {
-    const AdamArgs& a = c.a;
-    adam_wide_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
-                         c.nan_step, blockIdx.x, gridDim.x);
-}
-__global__ __launch_bounds__(256) void adam_wide_chk_kernel_m(const AdamChkArgs* t) {
-    const AdamChkArgs c = t[blockIdx.z];
-    const AdamArgs& a = c.a;
-    adam_wide_body<true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
-                         c.nan_step, blockIdx.x, gridDim.x);
-}
-
-// clipped instances (raae_optim_step_clip with a scale): the bodies above with SC = true, checked or not, narrow or wide
-template <bool CHK, bool WIDE>
-__device__ __forceinline__ void adam_clip_run(const AdamChkArgs& c) {
-    const AdamArgs& a = c.a;
-    if (WIDE) adam_wide_body<CHK, true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
-                                        c.nan_step, blockIdx.x, gridDim.x, a.gscale);
-    else adam_body<CHK, true>(a.p, a.m, a.v, a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.hyper, a.step, a.decoupled,
-                              c.nan_step, a.gscale);
-}
-template <bool CHK, bool WIDE> __global__ __launch_bounds__(256) void adam_clip_kernel(AdamChkArgs c) { adam_clip_run<CHK, WIDE>(c); }
-template <bool CHK, bool WIDE> __global__ __launch_bounds__(256) void adam_clip_kernel_m(const AdamChkArgs* t) {
-    const AdamChkArgs c = t[blockIdx.z];
-    adam_clip_run<CHK, WIDE>(c);
-}
-
-// ---- RAdam and AdaBound (torch_optimizer 0.1.0, the optimizer_name values the reference takes from that package) ----
-// One kernel instance per rule: OptRule<R>::scalars forms the per-step scalars in double (Python floats) from the
-// device hyper block and step count, in the operation order of the Python source (no contraction into fma there);
-// OptRule<R>::update is the per-element fp32 update in the order of the torch ops.  Gradient reading as in Adam.
-constexpr int OPT_NSC = 10;
-struct OptimArgs { float* p; float* m; float* v; const float* g_slabs; long slab_stride; const unsigned short* seg_nslab;
-                   long n; const double* hyper; const int* step;
-                   const float* gscale; };  // NULL, or the clip scale (AdamArgs::gscale)
-template <int RULE> struct OptRule;
-
-// torch_optimizer.RAdam.step.  The class caches (t, N, step size) in a 10-entry buffer keyed on t % 10, filled by the
-// first tensor stepped at a given t; every tensor of one optimizer here shares one step count, so the cache always
-// holds what the formula gives at the current lr, and the formula is evaluated directly.  N is formed in double in
-// this order: at t = 5 it misses 5 by only 4e-3 (beta2 = 0.999) or 4e-4 (0.9999); t = 6 is the first rectified step.
-template <> struct OptRule<RAAE_OPT_RADAM> {
-    __device__ static void scalars(const double* h, int step, float* s) {
-#pragma clang fp contract(off)
-        const double lr = h[0], b1 = h[1], b2 = h[2], eps = h[3], wd = h[4];
-        const double t = (double)step;
-        const double b2t = pow(b2, t);
-        const double nmax = 2.0 / (1.0 - b2) - 1.0;
-        const double nsma = nmax - 2.0 * t * b2t / (1.0 - b2t);
-        const bool rect = nsma >= 5.0;
-        const double ss = rect ? lr * sqrt((1.0 - b2t) * (nsma - 4.0) / (nmax - 4.0) * (nsma - 2.0) / nsma * nmax /
-                                           (nmax - 2.0)) / (1.0 - pow(b1, t))
-                               : lr / (1.0 - pow(b1, t));
-        s[0] = (float)b1;
-        s[1] = (float)(1.0 - b1);
-        s[2] = (float)b2;
-        s[3] = (float)(1.0 - b2);
-        s[4] = (float)(-ss);
-        s[5] = (float)eps;
-        s[6] = (float)(-wd * lr);           // decoupled decay: p.add_(p, alpha=-wd*lr)
-        s[7] = wd != 0.0 ? 1.f : 0.f;
-        s[8] = rect ? 1.f : 0.f;
-        s[9] = 0.f;
-    }
-    __device__ static void update(const float (&s)[OPT_NSC], float& p, float& m, float& v, float g) {
-        v = v * s[2];
-        v = v + (s[3] * g) * g;             // exp_avg_sq.mul_(b2).addcmul_(g, g, value=1-b2), before exp_avg
-        m = m * s[0];
-        m = m + s[1] * g;                   // exp_avg.mul_(b1).add_(g, alpha=1-b1)
-        if (s[7] != 0.f) p = p + s[6] * p;
-        if (s[8] != 0.f) p = p + (s[4] * m) / (sqrtf(v) + s[5]);   // addcdiv_(exp_avg, sqrt(v) + eps, value=-ss)
-        else p = p + s[4] * m;                                     // the first steps: SGD with momentum
-    }
-};
-
-// torch_optimizer.AdaBound.step (amsbound = False).  hyper[5] = base_lr (the lr at construction, self.base_lrs; a
-// ReduceLROnPlateau cut of hyper[0] moves the bounds through final_lr * lr / base_lr).
-template <> struct OptRule<RAAE_OPT_ADABOUND> {
-    __device__ static void scalars(const double* h, int step, float* s) {
-#pragma clang fp contract(off)
-        const double lr = h[0], b1 = h[1], b2 = h[2], eps = h[3], wd = h[4], base_lr = h[5], final_lr = h[6],
-                     gamma = h[7];
-        const double t = (double)step;
-        const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
-        const double ss = lr * sqrt(bc2) / bc1;
-        const double flr = final_lr * lr / base_lr;
-        s[0] = (float)b1;
-        s[1] = (float)(1.0 - b1);
-        s[2] = (float)b2;
-        s[3] = (float)(1.0 - b2);
-        s[4] = (float)ss;                                       // torch.full_like(denom, step_size)
-        s[5] = (float)(flr * (1.0 - 1.0 / (gamma * t + 1.0)));  // clamp_ bounds, as fp32 scalars
-        s[6] = (float)(flr * (1.0 + 1.0 / (gamma * t)));
-        s[7] = (float)eps;
-        s[8] = (float)wd;
-        s[9] = wd != 0.0 ? 1.f : 0.f;
-    }
-    __device__ static void update(const float (&s)[OPT_NSC], float& p, float& m, float& v, float g) {
-        if (s[9] != 0.f) g = g + s[8] * p;                 // grad.add(p, alpha=wd): coupled L2
-        m = m * s[0];
-        m = m + s[1] * g;
-        v = v * s[2];
-        v = v + (s[3] * g) * g;
-        float x = s[4] / (sqrtf(v) + s[7]);                // step_size.div_(denom).clamp_(lo, hi).mul_(exp_avg)
-        x = x < s[5] ? s[5] : (x > s[6] ? s[6] : x);       // (NaN passes through, as in torch.clamp)
-        x = x * m;
-        p = p + (-x);
-    }
-};
-
-template <int RULE>
-__device__ __forceinline__ void optim_scalars(const OptimArgs& a, float (&sc)[OPT_NSC]) {
-    __shared__ float s_sc[OPT_NSC];
-    if (threadIdx.x == 0) OptRule<RULE>::scalars(a.hyper, a.step[0], s_sc);
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < OPT_NSC; ++k) sc[k] = s_sc[k];
-}
-
-template <int RULE, bool CHK, bool SC = false>
-__device__ __forceinline__ void optim_body(const OptimArgs& a, int* nan_step) {
-    float sc[OPT_NSC];
-    optim_scalars<RULE>(a, sc);
-    bool seen = false;
-    float gs = 1.f;
-    if (SC) gs = a.gscale[0];
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
-        const int ns = a.seg_nslab[i >> 6];
-        if (ns == 0) continue;
-        float g = 0.f;                                  // adam_body's fixed-order slab sum
-        int s = 0;
-        for (; s + 8 <= ns; s += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = a.g_slabs[(size_t)(s + u) * a.slab_stride + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) g += t[u];
-        }
-        for (; s < ns; ++s) g += a.g_slabs[(size_t)s * a.slab_stride + i];
-        if (CHK) seen |= __builtin_isnan(g);
-        if (SC) g = scale_grad(g, gs);
-        float pv = a.p[i], mv = a.m[i], vv = a.v[i];
-        OptRule<RULE>::update(sc, pv, mv, vv, g);
-        a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
-    }
-    if (CHK) nan_vote(seen, nan_step, a.step);
-}
-
-template <int RULE, bool CHK, bool SC = false>
-__device__ __forceinline__ void optim_wide_body(const OptimArgs& a, int* nan_step) {
-    float sc[OPT_NSC];
-    optim_scalars<RULE>(a, sc);
-    float gs = 1.f;
-    if (SC) gs = a.gscale[0];
-    const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;   // adam_wide_body's lane split and shuffle tree
-    const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
-    bool seen = false;
-    for (long base = wave0; base < a.n; base += (long)gridDim.x * 32) {
-        const long i = base + el;                       // n is a multiple of 64: i < n whenever base < n
-        const int ns = a.seg_nslab[i >> 6];
-        if (ns == 0) continue;                          // uniform over the wave (8 elements share a segment)
-        float g = 0.f;
-        for (int s = ch; s < ns; s += 64) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int r = s + 8 * u;
-                t[u] = a.g_slabs[(size_t)(r < ns ? r : ch) * a.slab_stride + i];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) g += (s + 8 * u < ns) ? t[u] : 0.f;
-        }
-        g += __shfl_xor(g, 8, 64);
-        g += __shfl_xor(g, 16, 64);
-        g += __shfl_xor(g, 32, 64);
-        if (ch != 0) continue;
-        if (CHK) seen |= __builtin_isnan(g);
-        if (SC) g = scale_grad(g, gs);
-        float pv = a.p[i], mv = a.m[i], vv = a.v[i];
-        OptRule<RULE>::update(sc, pv, mv, vv, g);
-        a.p[i] = pv; a.m[i] = mv; a.v[i] = vv;
-    }
-    if (CHK) nan_vote(seen, nan_step, a.step);
-}
-
-template <int RULE> __global__ __launch_bounds__(256) void optim_kernel(OptimArgs a) { optim_body<RULE, false>(a, nullptr); }
-template <int RULE> __global__ __launch_bounds__(256) void optim_kernel_m(const OptimArgs* t) {
-    const OptimArgs a = t[blockIdx.z];
-    optim_body<RULE, false>(a, nullptr);
-}
-template <int RULE> __global__ __launch_bounds__(256) void optim_wide_kernel(OptimArgs a) { optim_wide_body<RULE, false>(a, nullptr); }
-template <int RULE> __global__ __launch_bounds__(256) void optim_wide_kernel_m(const OptimArgs* t) {
-    const OptimArgs a = t[blockIdx.z];
-    optim_wide_body<RULE, false>(a, nullptr);
-}
-// checked twins (raae_optim_step_chk)
-struct OptimChkArgs { OptimArgs a; int* nan_step; };
-template <int RULE> __global__ __launch_bounds__(256) void optim_chk_kernel(OptimChkArgs c) {
-    optim_body<RULE, true>(c.a, c.nan_step);
-}
-template <int RULE> __global__ __launch_bounds__(256) void optim_chk_kernel_m(const OptimChkArgs* t) {
-    const OptimChkArgs c = t[blockIdx.z];
-    optim_body<RULE, true>(c.a, c.nan_step);
-}
-template <int RULE> __global__ __launch_bounds__(256) void optim_wide_chk_kernel(OptimChkArgs c) {
-    optim_wide_body<RULE, true>(c.a, c.nan_step);
-}
-template <int RULE> __global__ __launch_bounds__(256) void optim_wide_chk_kernel_m(const OptimChkArgs* t) {
-    const OptimChkArgs c = t[blockIdx.z];
-    optim_wide_body<RULE, true>(c.a, c.nan_step);
-}
-
-// clipped instances (raae_optim_step_clip with a scale)
-template <int RULE, bool CHK, bool WIDE> __global__ __launch_bounds__(256) void optim_clip_kernel(OptimChkArgs c) {
-    if (WIDE) optim_wide_body<RULE, CHK, true>(c.a, c.nan_step); else optim_body<RULE, CHK, true>(c.a, c.nan_step);
-}
-template <int RULE, bool CHK, bool WIDE> __global__ __launch_bounds__(256) void optim_clip_kernel_m(const OptimChkArgs* t) {
-    const OptimChkArgs c = t[blockIdx.z];
-    if (WIDE) optim_wide_body<RULE, CHK, true>(c.a, c.nan_step); else optim_body<RULE, CHK, true>(c.a, c.nan_step);
-}
-
-// the grid of every update kernel: above 16 slabs 32 elements per workgroup (8 lanes per element), else one per thread
-inline dim3 optim_grid(long n, int max_nslab) {
-    long g = max_nslab > 16 ? (n + 31) / 32 : (n + 255) / 256;
-    if (g > 4096) g = 4096;
+// the shape and grid of every kernel that sums slabs (update, norm, reduce): above 16 slabs 8 lanes per element (32
+// elements per workgroup), else one element per thread; at most `cap` workgroups
+inline bool optim_wide(int max_nslab) { return max_nslab > 16; }
+inline dim3 optim_grid(long n, int max_nslab, long cap = 4096) {
+    long g = optim_wide(max_nslab) ? (n + 31) / 32 : (n + 255) / 256;
+    if (g > cap) g = cap;
     return dim3((int)g);
-}
-
-template <int RULE>
-void launch_optim(const OptimArgs& a, int max_nslab, hipStream_t stream) {
-    if (max_nslab > 16) {
-        long g = (a.n + 31) / 32;               // raae_adam_step's geometry
-        if (g > 4096) g = 4096;
-        raae::launch(optim_wide_kernel<RULE>, optim_wide_kernel_m<RULE>, dim3((int)g), dim3(256), 0, stream, a);
-    } else {
-        long g = (a.n + 255) / 256;
-        if (g > 4096) g = 4096;
-        raae::launch(optim_kernel<RULE>, optim_kernel_m<RULE>, dim3((int)g), dim3(256), 0, stream, a);
-    }
-}
-
-template <int RULE>
-void launch_optim_chk(const OptimChkArgs& c, int max_nslab, hipStream_t stream) {
-    if (max_nslab > 16)
-        raae::launch(optim_wide_chk_kernel<RULE>, optim_wide_chk_kernel_m<RULE>, optim_grid(c.a.n, max_nslab), dim3(256), 0,
-                     stream, c);
-    else
-        raae::launch(optim_chk_kernel<RULE>, optim_chk_kernel_m<RULE>, optim_grid(c.a.n, max_nslab), dim3(256), 0, stream, c);
-}
-
-template <int RULE>
-void launch_optim_clip(const OptimChkArgs& c, int max_nslab, hipStream_t stream) {
-    const dim3 grid = optim_grid(c.a.n, max_nslab), block(256);
-    if (max_nslab > 16) {
-        if (c.nan_step) raae::launch(optim_clip_kernel<RULE, true, true>, optim_clip_kernel_m<RULE, true, true>, grid, block, 0, stream, c);
-        else raae::launch(optim_clip_kernel<RULE, false, true>, optim_clip_kernel_m<RULE, false, true>, grid, block, 0, stream, c);
-    } else {
-        if (c.nan_step) raae::launch(optim_clip_kernel<RULE, true, false>, optim_clip_kernel_m<RULE, true, false>, grid, block, 0, stream, c);
-        else raae::launch(optim_clip_kernel<RULE, false, false>, optim_clip_kernel_m<RULE, false, false>, grid, block, 0, stream, c);
-    }
 }
 
 // ---- gradient-norm clipping (config key `grad_clip_norm`): the L2 norm of an optimizer's slab-summed gradient ----
@@ -368,46 +56,8 @@ __device__ __forceinline__ void grad_norm_body(const GradNormArgs& a) {
     __shared__ double s_red[16];
     __shared__ unsigned s_last;
     double acc = 0.0;
-    if (!WIDE) {
-        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < a.n; i += (long)gridDim.x * 256) {
-            const int ns = a.seg_nslab[i >> 6];
-            if (ns == 0) continue;
-            float g = 0.f;                                  // adam_body's fixed-order slab sum
-            int s = 0;
-            for (; s + 8 <= ns; s += 8) {
-                float t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) t[u] = a.g_slabs[(size_t)(s + u) * a.slab_stride + i];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) g += t[u];
-            }
-            for (; s < ns; ++s) g += a.g_slabs[(size_t)s * a.slab_stride + i];
-            acc += (double)g * (double)g;
-        }
-    } else {
-        const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;   // adam_wide_body's lane split and shuffle tree
-        const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
-        for (long base = wave0; base < a.n; base += (long)gridDim.x * 32) {
-            const long i = base + el;                       // n is a multiple of 64: i < n whenever base < n
-            const int ns = a.seg_nslab[i >> 6];
-            if (ns == 0) continue;                          // uniform over the wave (8 elements share a segment)
-            float g = 0.f;
-            for (int s = ch; s < ns; s += 64) {
-                float t[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int r = s + 8 * u;
-                    t[u] = a.g_slabs[(size_t)(r < ns ? r : ch) * a.slab_stride + i];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) g += (s + 8 * u < ns) ? t[u] : 0.f;
-            }
-            g += __shfl_xor(g, 8, 64);
-            g += __shfl_xor(g, 16, 64);
-            g += __shfl_xor(g, 32, 64);
-            if (ch == 0) acc += (double)g * (double)g;
-        }
-    }
+    for_each_grad<WIDE, false>(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, blockIdx.x, gridDim.x,
+                               [&](long, float g) { acc += (double)g * (double)g; });
     const double part = raae::block_sum(acc, s_red);
     if (threadIdx.x == 0) {
         a.partial[blockIdx.x] = part;
@@ -430,15 +80,26 @@ __device__ __forceinline__ void grad_norm_body(const GradNormArgs& a) {
         *a.ticket = 0u;
     }
 }
-__global__ __launch_bounds__(256) void grad_norm_kernel(GradNormArgs a) { grad_norm_body<false>(a); }
-__global__ __launch_bounds__(256) void grad_norm_kernel_m(const GradNormArgs* t) {
+template <bool WIDE> __global__ __launch_bounds__(256) void grad_norm_kernel(GradNormArgs a) { grad_norm_body<WIDE>(a); }
+template <bool WIDE> __global__ __launch_bounds__(256) void grad_norm_kernel_m(const GradNormArgs* t) {
     const GradNormArgs a = t[blockIdx.z];
-    grad_norm_body<false>(a);
+    grad_norm_body<WIDE>(a);
 }
-__global__ __launch_bounds__(256) void grad_norm_wide_kernel(GradNormArgs a) { grad_norm_body<true>(a); }
-__global__ __launch_bounds__(256) void grad_norm_wide_kernel_m(const GradNormArgs* t) {
-    const GradNormArgs a = t[blockIdx.z];
-    grad_norm_body<true>(a);
+
+// ---- the data-parallel helper: out[i] = the slab sum of element i, 0 for a segment without slabs ----
+// Summed as the update sums, so that the data-parallel path adds the slabs of a rank in exactly the order the
+// single-GPU update does.
+// (argument block + `_m` twins: with `grad_clip_norm` the flat gradient is part of a batched trial's step too)
+struct SlabReduceArgs { const float* g_slabs; long slab_stride; const unsigned short* seg_nslab; long n; float* out; };
+template <bool WIDE>
+__device__ __forceinline__ void slab_reduce_body(const SlabReduceArgs& a) {
+    for_each_grad<WIDE, true>(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, blockIdx.x, gridDim.x,
+                              [&](long i, float g) { a.out[i] = g; });
+}
+template <bool WIDE> __global__ __launch_bounds__(256) void slab_reduce_kernel(SlabReduceArgs a) { slab_reduce_body<WIDE>(a); }
+template <bool WIDE> __global__ __launch_bounds__(256) void slab_reduce_kernel_m(const SlabReduceArgs* t) {
+    const SlabReduceArgs a = t[blockIdx.z];
+    slab_reduce_body<WIDE>(a);
 }
 
 // ---- moving average of the weights (config key `ema_decay`): ema[i] = fmaf(d, ema[i], omd * p[i]) ----
@@ -636,80 +297,38 @@ __global__ __launch_bounds__(256) void step_begin_kernel_m(const StepBeginArgs* 
 
 }  // namespace
 
-extern "C" int raae_adam_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
-                              const unsigned short* seg_nslab, long n, const double* hyper, const int* step,
-                              int decoupled, int max_nslab, void* stream) {
-    RAAE_CHECK_ARG(p && m && v && g_slabs && seg_nslab && hyper && step && n > 0 && (n % 64) == 0 && max_nslab >= 0);
-    const AdamArgs a = {p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, decoupled};
-    if (max_nslab > 16) {
-        long g = (n + 31) / 32;                 // 32 elements per workgroup (8 lanes per element)
-        if (g > 4096) g = 4096;
-        raae::launch(adam_wide_kernel, adam_wide_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        long g = (n + 255) / 256;               // one element per thread
-        if (g > 4096) g = 4096;
-        raae::launch(adam_kernel, adam_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
-    }
-    RAAE_LAUNCH_RET();
-}
-
-extern "C" int raae_optim_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
-                               const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
-                               int max_nslab, void* stream) {
+// The one launch path of the update, and the entry of a clipped one: the rule picks the family, max_nslab the shape and
+// the grid, nan_step != NULL the checked and scale != NULL the clipped variant.  The entries without a flag word or a
+// scale pass NULL: the same kernel, the same grid (raae_multi_build compares both across trials).
+extern "C" int raae_optim_step_clip(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                                    const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
+                                    int max_nslab, int* nan_step, const float* scale, void* stream) {
     RAAE_CHECK_ARG(rule >= RAAE_OPT_ADAM && rule <= RAAE_OPT_ADABOUND);
-    if (rule == RAAE_OPT_ADAM || rule == RAAE_OPT_ADAMW)
-        return raae_adam_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, rule == RAAE_OPT_ADAMW,
-                              max_nslab, stream);
     RAAE_CHECK_ARG(p && m && v && g_slabs && seg_nslab && hyper && step && n > 0 && (n % 64) == 0 && max_nslab >= 0);
-    const OptimArgs a = {p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step};
-    if (rule == RAAE_OPT_RADAM) launch_optim<RAAE_OPT_RADAM>(a, max_nslab, (hipStream_t)stream);
-    else launch_optim<RAAE_OPT_ADABOUND>(a, max_nslab, (hipStream_t)stream);
+    const UpdateArgs a = {p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, rule == RAAE_OPT_ADAMW, scale, nan_step};
+    const UpdateInst& k = kUpdate[rule][optim_wide(max_nslab)][nan_step != nullptr][scale != nullptr];
+    raae::launch(k.single, k.multi, optim_grid(n, max_nslab), dim3(256), 0, (hipStream_t)stream, a);
     RAAE_LAUNCH_RET();
 }
 
 extern "C" int raae_optim_step_chk(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
                                    const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
                                    int max_nslab, int* nan_step, void* stream) {
-    RAAE_CHECK_ARG(rule >= RAAE_OPT_ADAM && rule <= RAAE_OPT_ADABOUND && nan_step);
-    RAAE_CHECK_ARG(p && m && v && g_slabs && seg_nslab && hyper && step && n > 0 && (n % 64) == 0 && max_nslab >= 0);
-    const hipStream_t st = (hipStream_t)stream;
-    if (rule == RAAE_OPT_ADAM || rule == RAAE_OPT_ADAMW) {
-        const AdamChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, rule == RAAE_OPT_ADAMW}, nan_step};
-        if (max_nslab > 16) raae::launch(adam_wide_chk_kernel, adam_wide_chk_kernel_m, optim_grid(n, max_nslab), dim3(256), 0, st, c);
-        else raae::launch(adam_chk_kernel, adam_chk_kernel_m, optim_grid(n, max_nslab), dim3(256), 0, st, c);
-    } else {
-        const OptimChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step}, nan_step};
-        if (rule == RAAE_OPT_RADAM) launch_optim_chk<RAAE_OPT_RADAM>(c, max_nslab, st);
-        else launch_optim_chk<RAAE_OPT_ADABOUND>(c, max_nslab, st);
-    }
-    RAAE_LAUNCH_RET();
+    RAAE_CHECK_ARG(nan_step);
+    return raae_optim_step_clip(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab, nan_step, nullptr, stream);
 }
 
-extern "C" int raae_optim_step_clip(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
-                                    const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
-                                    int max_nslab, int* nan_step, const float* scale, void* stream) {
-    if (scale == nullptr)               // no scale: the entries without one, launch for launch
-        return nan_step ? raae_optim_step_chk(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab, nan_step, stream)
-                        : raae_optim_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab, stream);
-    RAAE_CHECK_ARG(rule >= RAAE_OPT_ADAM && rule <= RAAE_OPT_ADABOUND);
-    RAAE_CHECK_ARG(p && m && v && g_slabs && seg_nslab && hyper && step && n > 0 && (n % 64) == 0 && max_nslab >= 0);
-    const hipStream_t st = (hipStream_t)stream;
-    if (rule == RAAE_OPT_ADAM || rule == RAAE_OPT_ADAMW) {
-        const AdamChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, rule == RAAE_OPT_ADAMW, scale}, nan_step};
-        const dim3 grid = optim_grid(n, max_nslab), block(256);
-        if (max_nslab > 16) {
-            if (nan_step) raae::launch(adam_clip_kernel<true, true>, adam_clip_kernel_m<true, true>, grid, block, 0, st, c);
-            else raae::launch(adam_clip_kernel<false, true>, adam_clip_kernel_m<false, true>, grid, block, 0, st, c);
-        } else {
-            if (nan_step) raae::launch(adam_clip_kernel<true, false>, adam_clip_kernel_m<true, false>, grid, block, 0, st, c);
-            else raae::launch(adam_clip_kernel<false, false>, adam_clip_kernel_m<false, false>, grid, block, 0, st, c);
-        }
-    } else {
-        const OptimChkArgs c = {{p, m, v, g_slabs, slab_stride, seg_nslab, n, hyper, step, scale}, nan_step};
-        if (rule == RAAE_OPT_RADAM) launch_optim_clip<RAAE_OPT_RADAM>(c, max_nslab, st);
-        else launch_optim_clip<RAAE_OPT_ADABOUND>(c, max_nslab, st);
-    }
-    RAAE_LAUNCH_RET();
+extern "C" int raae_optim_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                               const unsigned short* seg_nslab, long n, int rule, const double* hyper, const int* step,
+                               int max_nslab, void* stream) {
+    return raae_optim_step_clip(p, m, v, g_slabs, slab_stride, seg_nslab, n, rule, hyper, step, max_nslab, nullptr, nullptr, stream);
+}
+
+extern "C" int raae_adam_step(float* p, float* m, float* v, const float* g_slabs, long slab_stride,
+                              const unsigned short* seg_nslab, long n, const double* hyper, const int* step,
+                              int decoupled, int max_nslab, void* stream) {
+    return raae_optim_step(p, m, v, g_slabs, slab_stride, seg_nslab, n, decoupled ? RAAE_OPT_ADAMW : RAAE_OPT_ADAM, hyper, step,
+                           max_nslab, stream);
 }
 
 extern "C" int raae_grad_norm(const float* g_slabs, long slab_stride, const unsigned short* seg_nslab, long n, int max_nslab,
@@ -717,10 +336,19 @@ extern "C" int raae_grad_norm(const float* g_slabs, long slab_stride, const unsi
     RAAE_CHECK_ARG(g_slabs && seg_nslab && partial && ticket && out && clipped && n > 0 && (n % 64) == 0 && max_nslab >= 0);
     RAAE_CHECK_ARG(max_norm > 0.0 && max_norm <= 1.7976931348623157e308);      // finite, > 0 (false for NaN)
     const GradNormArgs a = {g_slabs, slab_stride, seg_nslab, n, max_norm, partial, ticket, out, clipped};
-    long g = max_nslab > 16 ? (n + 31) / 32 : (n + 255) / 256;      // the update kernels' split of the elements ...
-    if (g > GRAD_NORM_PARTS) g = GRAD_NORM_PARTS;                   // ... over at most as many workgroups as `partial` holds
-    if (max_nslab > 16) raae::launch(grad_norm_wide_kernel, grad_norm_wide_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
-    else raae::launch(grad_norm_kernel, grad_norm_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
+    const dim3 grid = optim_grid(n, max_nslab, GRAD_NORM_PARTS);    // at most as many workgroups as `partial` holds
+    if (optim_wide(max_nslab)) raae::launch(grad_norm_kernel<true>, grad_norm_kernel_m<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else raae::launch(grad_norm_kernel<false>, grad_norm_kernel_m<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    RAAE_LAUNCH_RET();
+}
+
+extern "C" int raae_slab_reduce(const float* g_slabs, long slab_stride, const unsigned short* seg_nslab, long n,
+                                float* out, int max_nslab, void* stream) {
+    RAAE_CHECK_ARG(g_slabs && seg_nslab && out && n > 0 && (n % 64) == 0 && max_nslab >= 0);
+    const SlabReduceArgs a = {g_slabs, slab_stride, seg_nslab, n, out};
+    const dim3 grid = optim_grid(n, max_nslab);
+    if (optim_wide(max_nslab)) raae::launch(slab_reduce_kernel<true>, slab_reduce_kernel_m<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+    else raae::launch(slab_reduce_kernel<false>, slab_reduce_kernel_m<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
     RAAE_LAUNCH_RET();
 }
 
@@ -828,86 +456,6 @@ extern "C" int raae_abi_version(void) { return RAAE_ABI_VERSION; }
 #define RAAE_SOURCE_DIGEST "unknown"
 #endif
 extern "C" const char* raae_source_digest(void) { return RAAE_SOURCE_DIGEST; }
-
-// ---------------------------------------------------------------- data-parallel helper
-namespace {
-// (argument block + `_m` twins: with `grad_clip_norm` the flat gradient is part of a batched trial's step too)
-struct SlabReduceArgs { const float* g_slabs; long slab_stride; const unsigned short* seg_nslab; long n; float* out; };
-__device__ __forceinline__ void slab_reduce_body(const float* g_slabs, long slab_stride,
-                                                 const unsigned short* seg_nslab, long n, float* out) {
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const int ns = seg_nslab[i >> 6];
-        float g = 0.f;
-        int s = 0;
-        for (; s + 8 <= ns; s += 8) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t[u] = g_slabs[(size_t)(s + u) * slab_stride + i];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) g += t[u];
-        }
-        for (; s < ns; ++s) g += g_slabs[(size_t)s * slab_stride + i];
-        out[i] = g;
-    }
-}
-// the summation tree of adam_wide_kernel (8 lanes per element), so that the data-parallel path adds the
-// slabs of a rank in exactly the order the single-GPU update does
-__device__ __forceinline__ void slab_reduce_wide_body(const float* g_slabs, long slab_stride,
-                                                      const unsigned short* seg_nslab, long n, float* out) {
-    const int lane = threadIdx.x & 63, el = lane & 7, ch = lane >> 3;
-    const long wave0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
-    for (long base = wave0; base < n; base += (long)gridDim.x * 32) {
-        const long i = base + el;
-        const int ns = seg_nslab[i >> 6];
-        float g = 0.f;
-        for (int s = ch; s < ns; s += 64) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int r = s + 8 * u;
-                t[u] = g_slabs[(size_t)(r < ns ? r : ch) * slab_stride + i];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) g += (s + 8 * u < ns) ? t[u] : 0.f;
-        }
-        g += __shfl_xor(g, 8, 64);
-        g += __shfl_xor(g, 16, 64);
-        g += __shfl_xor(g, 32, 64);
-        if (ch == 0) out[i] = g;
-    }
-}
-__global__ __launch_bounds__(256) void slab_reduce_kernel(SlabReduceArgs a) {
-    slab_reduce_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
-}
-__global__ __launch_bounds__(256) void slab_reduce_kernel_m(const SlabReduceArgs* t) {
-    const SlabReduceArgs a = t[blockIdx.z];
-    slab_reduce_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
-}
-__global__ __launch_bounds__(256) void slab_reduce_wide_kernel(SlabReduceArgs a) {
-    slab_reduce_wide_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
-}
-__global__ __launch_bounds__(256) void slab_reduce_wide_kernel_m(const SlabReduceArgs* t) {
-    const SlabReduceArgs a = t[blockIdx.z];
-    slab_reduce_wide_body(a.g_slabs, a.slab_stride, a.seg_nslab, a.n, a.out);
-}
-}  // namespace
-
-extern "C" int raae_slab_reduce(const float* g_slabs, long slab_stride, const unsigned short* seg_nslab, long n,
-                                float* out, int max_nslab, void* stream) {
-    RAAE_CHECK_ARG(g_slabs && seg_nslab && out && n > 0 && (n % 64) == 0 && max_nslab >= 0);
-    const SlabReduceArgs a = {g_slabs, slab_stride, seg_nslab, n, out};
-    if (max_nslab > 16) {
-        long g = (n + 31) / 32;
-        if (g > 4096) g = 4096;
-        raae::launch(slab_reduce_wide_kernel, slab_reduce_wide_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        long g = (n + 255) / 256;
-        if (g > 4096) g = 4096;
-        raae::launch(slab_reduce_kernel, slab_reduce_kernel_m, dim3((int)g), dim3(256), 0, (hipStream_t)stream, a);
-    }
-    RAAE_LAUNCH_RET();
-}
-
 
 // ---------------------------------------------------------------- batched launches over trials (raae_common.h)
 #include <cstdio>

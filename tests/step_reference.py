@@ -1,5 +1,5 @@
-"""Float64 / Python-integer reference of ``csrc/raae_optim.hip`` with ``raae_adam_body.inc``: the four update rules, the
-slab sum, the random tape (Philox4x32-10, ``u01``, Box-Muller; the mask kinds through ``dense_reference.mask_hash``),
+"""Float64 / Python-integer reference of ``csrc/raae_optim.hip`` with ``raae_optim_body.inc``: the four update rules
+(``OptRule<R>::scalars`` / ``::update`` under ``update_body``), the slab sum (``slab_sum`` / ``slab_sum_wide``), the random tape (Philox4x32-10, ``u01``, Box-Muller; the mask kinds through ``dense_reference.mask_hash``),
 ``raae_step_tick`` and ``raae_step_begin`` -- with a mirror of the dispatch (which kernel shape and grid a call takes).
 Plain numpy, no autograd, nothing imported from the package.  The oracle of ``test_step_kernels_gpu.py``;
 ``test_step_reference_cpu.py`` pins it to ``torch.optim`` / ``optim_reference`` in float64 and to the Random123
@@ -39,8 +39,8 @@ M32 = 0xFFFFFFFF
 
 # ------------------------------------------------------------------------------------------------------ dispatch mirror
 def update_form(n, max_nslab):
-    """(shape, grid) of every update kernel and of ``raae_slab_reduce``: one thread per element, or 8 lanes per element
-    (32 elements per workgroup) above 16 slabs; at most 4096 workgroups."""
+    """(shape, grid) of every update kernel and of ``raae_slab_reduce`` (``optim_grid``): one thread per element, or 8
+    lanes per element (32 elements per workgroup) above 16 slabs; at most 4096 workgroups."""
     if max_nslab > LANES8_ABOVE:
         return "lanes8", min(GRID_CAP, (n + 31) // 32)
     return "thread", min(GRID_CAP, (n + 255) // 256)

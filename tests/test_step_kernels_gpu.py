@@ -1,5 +1,6 @@
-"""Every kernel form of ``csrc/raae_optim.hip`` with ``raae_adam_body.inc`` -- the 32 update instances (4 rules x
-{one thread per element, 8 lanes per element} x {plain, checked, clipped, checked + clipped}) and their ``_m`` twins,
+"""Every kernel form of ``csrc/raae_optim.hip`` with ``raae_optim_body.inc`` -- the 32 update instances (4 rules x
+{one thread per element, 8 lanes per element} x {plain, checked, clipped, checked + clipped}: ``update_body<RULE, WIDE,
+CHK, SC>`` under ``update_kernel``, Adam and AdamW sharing a family) and their ``_m`` twins,
 ``raae_slab_reduce``, the Gaussian half of ``raae_rng_fill``, ``raae_step_tick`` and ``raae_step_begin`` -- against the
 float64 / Python-integer reference of ``step_reference``, one launch at a time, teacher-forced.
 
