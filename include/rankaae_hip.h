@@ -776,6 +776,35 @@ int raae_spec_augment3(const float* spec, const long* idx, const int* cursor, co
                        int B, int L, double max_sigma, double max_shift, double max_gain, double max_tilt,
                        double spec_noise, long noise_goff, float* spec_out, void* stream);
 
+/* ---- applying trained models to foreign spectra (ABI 34; rankaae_amd/apply.py, DESIGN.md "Applying the models") ----
+ * raae_resample_rows: rows on a foreign energy grid onto the model's, by a plan the host makes once from the two grids:
+ *     out[r][l] = fmaf(w[l], src[r][idx[l] + 1] - src[r][idx[l]], src[r][idx[l]])
+ * src [n][ld_src] fp32 (Ls used), idx [L] int32 with 0 <= idx[l] <= Ls - 2 (the kernel clamps: a broken plan reads no
+ * byte outside its row), w [L] fp32 with 0 <= w[l] <= 1, out [n][ld_out] fp32 (L used).  w[l] == 0 gives
+ * src[r][idx[l]] and w[l] == 1 gives src[r][idx[l] + 1] bit for bit (a select, no arithmetic); any other w is the one
+ * fmaf, |error| <= 5 * 2^-24 * max(|a|, |b|) with the rounding of w to fp32 counted.  src and out must not overlap.
+ *   n >= 1, 2 <= Ls <= 65536, 1 <= L <= 4096, ld_src >= Ls, ld_out >= L, no NULL pointer.  Anything else: RAAE_EINVAL,
+ *   nothing is launched.
+ * raae_ensemble_stats: what J models say about each of n rows, one launch.  z[j] -> [n][k] fp32 styles and recon[j] ->
+ * [n][L] fp32 reconstructions of model j (z and recon are DEVICE arrays of J device pointers), spec [n][L] fp32 the
+ * common input, calib [J][n_aux][4] doubles {kind, p0, p1, 0} per model and descriptor: kind 0 no fit, kind 1
+ * d = (z - p1) / p0 (p0 the slope, p1 the intercept of linregress with x = descriptor, y = style), kind 2
+ * d = 4 + (z > p0) + (z > p1) (the CN45 and CN56 thresholds); descriptor i reads style i, i < min(k, n_aux).  Outputs,
+ * doubles: z_mean, z_std [n][k]; d_mean, d_std [n][n_aux] over the models whose kind is not 0, d_used [n_aux] their
+ * number (0: d_mean and d_std are NaN; so they are for a descriptor i >= k); mae[j * ld_mae + r] the mean over l of
+ * |recon[j][r][l] - spec[r][l]| (the difference in fp32, summed in double); mae_mean [n] its mean over the models.
+ * Standard deviations are sample (ddof = 1), two-pass, exactly 0 where one model contributes; every sum is double and
+ * in a fixed order, no atomics.
+ *   1 <= J <= 64, n >= 1, 1 <= k <= 16, 0 <= n_aux <= 16, L >= 1, ld_mae >= n, no NULL pointer (calib, d_mean, d_std,
+ *   d_used may be NULL when n_aux == 0).  Anything else: RAAE_EINVAL, nothing is launched.
+ * Both go through the recorded-launch path like every kernel; neither is meant to be recorded once per model (they
+ * run once over all J). */
+int raae_resample_rows(const float* src, int n, int Ls, int ld_src, const int* idx, const float* w, int L, float* out,
+                       int ld_out, void* stream);
+int raae_ensemble_stats(const float* const* z, const float* spec, const float* const* recon, const double* calib, int J,
+                        int n, int k, int n_aux, int L, double* z_mean, double* z_std, double* d_mean, double* d_std,
+                        double* d_used, double* mae, long ld_mae, double* mae_mean, void* stream);
+
 /* ---- independent trials batched into one launch (reference: sc/cmd/train_sc.py:127-143 maps `trials` over
  * engines) ----
  * The entry points of the dense-network path (raae_step_begin, raae_dense_fwd_s / _fwd2 / _bwd_s, raae_style_bn_*,
@@ -824,7 +853,7 @@ int raae_event_destroy(void* ev);
 int raae_stream_sync(void* stream);
 const char* raae_error_string(int code);
 int raae_device_info(int* cu_count, int* lds_bytes, char* name, int name_len);
-#define RAAE_ABI_VERSION 33
+#define RAAE_ABI_VERSION 34
 int raae_abi_version(void);
 /* First 16 hex digits of sha256 over include/rankaae_hip.h + csrc/raae_*.{h,inc,hip} at build time
  * (build.sh); the Python loader recomputes it and refuses a library built from other sources. */

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "librankaae_hip.so")
 
 RAAE_MAX_PARTS = 512
-ABI_VERSION = 33
+ABI_VERSION = 34
 IN_NONE, IN_PRELU_BN_DROP, IN_PRELU_DROP = 0, 1, 2
 OUT_RAW, OUT_STATS_PRELU, OUT_STATS_RAW, OUT_SOFTPLUS, OUT_RELU = 0, 1, 2, 3, 4
 G_DIRECT, G_SOFTPLUS, G_PRELU_BN, G_PRELU, G_RELU = 0, 1, 2, 3, 4
@@ -266,6 +266,8 @@ SIGNATURES = {
     "raae_spec_augment2": (_I, [_P, _P, _P, _P, _I, _I, C.c_double, C.c_double, C.c_double, _L, _P, _P]),
     "raae_spec_augment3": (_I, [_P, _P, _P, _P, _I, _I, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _L,
                            _P, _P]),
+    "raae_resample_rows": (_I, [_P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
+    "raae_ensemble_stats": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P, _P]),
     "raae_rng_fill": (_I, [_P, _P, _P, _I, _L, C.c_ulonglong, _P, _P]),
     "raae_record_begin": (_I, []),
     "raae_record_end": (_I, [C.POINTER(C.c_void_p), _PI]),

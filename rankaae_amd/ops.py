@@ -314,6 +314,43 @@ def select_scores(styles, n, k, aux, n_aux, spec_in, spec_out, L, thresh, work, 
                                      _ptr(out, torch.float64), _stream()), name)
 
 
+def resample_rows(src, idx, w, out):
+    """``raae_resample_rows``: ``src [n, Ls]`` fp32 rows (a row stride >= Ls is taken as the leading dimension) onto
+    ``out [n, L]`` by the plan ``idx [L]`` int32, ``w [L]`` fp32 (``rankaae_amd.apply.resample_plan``)."""
+    assert src.is_cuda and out.is_cuda and src.dtype == out.dtype == torch.float32 and src.dim() == out.dim() == 2
+    assert src.stride(1) == 1 and out.stride(1) == 1 and src.shape[0] == out.shape[0]
+    n, Ls = src.shape
+    L = out.shape[1]
+    assert idx.numel() == L and w.numel() == L
+    ld_src = src.stride(0) if n > 1 else max(src.stride(0), Ls)
+    ld_out = out.stride(0) if n > 1 else max(out.stride(0), L)
+    check(_lib.load().raae_resample_rows(C.c_void_p(src.data_ptr()), n, Ls, ld_src, _ptr(idx, torch.int32), _ptr(w), L,
+                                         C.c_void_p(out.data_ptr()), ld_out, _stream()), "raae_resample_rows")
+
+
+def pointer_table(tensors):
+    """A device array of the tensors' device addresses (``const float* const*`` of ``raae_ensemble_stats``).  The
+    caller keeps the tensors alive."""
+    return torch.tensor([t.data_ptr() for t in tensors], dtype=torch.int64).to(tensors[0].device)
+
+
+def ensemble_stats(z_tab, spec, recon_tab, calib, J, n, k, n_aux, L, z_mean, z_std, d_mean, d_std, d_used, mae, ld_mae,
+                   mae_mean):
+    """``raae_ensemble_stats`` over ``n`` rows: ``z_tab`` / ``recon_tab`` are ``pointer_table`` s of the J models'
+    contiguous ``[n, k]`` styles and ``[n, L]`` reconstructions, ``calib [J, n_aux, 4]`` float64; the outputs are
+    float64 (``mae`` may be a view into ``[J, ld_mae]`` at a row offset)."""
+    assert z_tab.numel() == J and recon_tab.numel() == J and spec.numel() == n * L
+    assert z_mean.numel() >= n * k and z_std.numel() >= n * k and mae_mean.numel() >= n
+    if n_aux:
+        assert calib.numel() == J * n_aux * 4 and d_mean.numel() >= n * n_aux and d_std.numel() >= n * n_aux
+        assert d_used.numel() == n_aux
+    f64 = lambda t: _ptr(t, torch.float64) if n_aux else None      # noqa: E731
+    check(_lib.load().raae_ensemble_stats(_ptr(z_tab, torch.int64), _ptr(spec), _ptr(recon_tab, torch.int64), f64(calib),
+                                          J, n, k, n_aux, L, _ptr(z_mean, torch.float64), _ptr(z_std, torch.float64),
+                                          f64(d_mean), f64(d_std), f64(d_used), C.c_void_p(mae.data_ptr()), ld_mae,
+                                          _ptr(mae_mean, torch.float64), _stream()), "raae_ensemble_stats")
+
+
 def _fin(fin):
     """``fin = (scale, out, slot, acc_slot, ticket)``: the loss is finished inside the kernel (``raae_loss_fin_t``);
     None: the partials are left for ``loss_finalize``."""

@@ -222,6 +222,28 @@ def report_weights_of(cfg):
     return value
 
 
+def _int_key(cfg, key, least, default):
+    value = cfg.get(key, None)
+    if value is None:
+        return default
+    if isinstance(value, bool) or not isinstance(value, int) or value < least:
+        raise ValueError(f"{key} must be an integer >= {least}, not {value!r}")
+    return value
+
+
+def apply_keys_of(cfg):
+    """The build-only keys of ``rankaae_amd.cmd.apply``: ``apply_top_n`` (an integer >= 1, default ``top_n``: how many of
+    the best-ranked trials are applied), ``apply_max_outside`` (an integer >= 0, default 0: how many points of the
+    model's energy grid may lie outside the input's range and take its edge value) and ``apply_chunk_rows`` (an integer
+    >= 1, default 16384: rows per pass of the models).  Returns ``(apply_top_n, apply_max_outside, apply_chunk_rows)``."""
+    top_n = _int_key(cfg, "apply_top_n", 1, None)
+    if top_n is None:
+        top_n = _int_key(cfg, "top_n", 1, None)
+        if top_n is None:
+            raise ValueError("apply_top_n: absent, and there is no top_n to default to")
+    return top_n, _int_key(cfg, "apply_max_outside", 0, 0), _int_key(cfg, "apply_chunk_rows", 1, 16384)
+
+
 def detect_anomaly_on(cfg):
     """Build-only key ``detect_anomaly`` (default ``true``: the reference turns on
     ``torch.autograd.set_detect_anomaly(True)`` at import, sc/clustering/trainer.py:11).  On, the optimizer updates

@@ -298,15 +298,17 @@ def load_model(jobs_dir, job, weights="final"):
     return torch.load(path, map_location="cpu", weights_only=False)
 
 
-def evaluate_all_models(jobs_dir, test_ds, device=None, batched=True, info=None, weights="final"):
+def evaluate_all_models(jobs_dir, test_ds, device=None, batched=True, info=None, weights="final", names=None):
     """``analysis.evaluate_all_models`` (analysis.py:105-123): ``{job: result dict}`` for every ``job_*`` under
     ``jobs_dir``, in sorted name order.  With ``batched`` and jobs of one architecture, the J eval forwards and the J
     score sequences are replayed as one launch sequence with ``gridDim.z = J``; otherwise (or if the recorder refuses)
     one job after the other.  The numbers are the same either way: a grid plane runs the kernel body a model runs
     alone.  ``info``: a dict that receives ``mode`` ("batched" / "sequential") and ``launches``.  ``weights``: "final"
-    (``final.pt``) or "ema" (``final_ema.pt`` of every job, ``load_model``)."""
+    (``final.pt``) or "ema" (``final_ema.pt`` of every job, ``load_model``).  ``names``: evaluate these jobs, in this
+    order, instead of every job.  An ``info`` that comes in with a key ``"blocks"`` gets ``{job: block}`` there, the
+    unrounded ``raae_select_scores`` blocks the results were rounded from (``rankaae_amd.apply.calibration``)."""
     device = device or torch.device("cuda:0")
-    names = list_jobs(jobs_dir)
+    names = list_jobs(jobs_dir) if names is None else [str(j) for j in names]
     if not names:
         raise FileNotFoundError(f"no job_*/final.pt under {jobs_dir}")
     stream = torch.cuda.Stream(device=device)
@@ -314,6 +316,7 @@ def evaluate_all_models(jobs_dir, test_ds, device=None, batched=True, info=None,
     models = [load_model(jobs_dir, j, weights) for j in names]       # (before any engine exists: a missing file raises here)
     jobs = [_Job(engine_from_model(m, test_ds, device, stream=stream), test_ds) for m in models]
     info = info if info is not None else {}
+    want_blocks = "blocks" in info
     info.update(mode="sequential", launches=0)
     with torch.cuda.stream(stream):
         prog = None
@@ -329,6 +332,8 @@ def evaluate_all_models(jobs_dir, test_ds, device=None, batched=True, info=None,
             prog.launch()
             info.update(mode="batched", launches=prog.count())
         result = OrderedDict((name, j.result()) for name, j in zip(names, jobs))
+        if want_blocks:
+            info["blocks"] = OrderedDict((name, j.scorer.read()) for name, j in zip(names, jobs))
     if prog is not None:
         prog.release()
     for j in jobs:
